@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Hot-path benchmark: DeepEP normal dispatch (INT8) + combine (BF16) on MI355X, BASELINE.json config C2 shapes.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 One step = one pass of the hot path over one batch of synthetic tokens on every rank:
@@ -42,6 +42,7 @@ XGMI_LINK_GBPS = 153.0          # per link, 7 links per GPU
 INT8_PEAK_TOPS = 3900.0         # dense int8 MFMA peak used in DESIGN.md (half the fp8 figure is quoted for bf16)
 T_TOKENS, HIDDEN, TOPK, EXPERTS = 4096, 7168, 8, 256
 INTER = 2048                    # DeepSeek-V3 MoE intermediate size (2I = 4096)
+DUMP_ROWS = 512                 # --dump-outputs: rows sampled from each [rows, hidden] output, shared out over the ranks (< 64 MB in all)
 
 
 def parse():
@@ -57,7 +58,14 @@ def parse():
     ap.add_argument("--dry-run-8", action="store_true",
                     help="plumbing check of the 8-GPU launch on ONE GPU: re-executes itself as 8 ranks that all use cuda:0 (gloo bootstrap, "
                          "hipIpc windows), full C2 size; the JSON line carries every N > 1 key and \"dry_run_single_device\": true -- NOT a measurement")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32 / "
+                         "float64; at N > 1 every rank writes <name>_rank<r>.npy): the layout tables, the received rows' per-expert "
+                         "counts and scales, and a fixed, seeded sample of rows of the INT8 dispatch and the BF16 combine outputs")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch_command(args, environ):
@@ -80,6 +88,8 @@ def self_launch_command(args, environ):
                      ("--no-cpu-baseline", args.no_cpu_baseline)):
         if on:
             cmd.append(flag)
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     return cmd, env
 
 
@@ -127,7 +137,7 @@ def one_step(buf, x, topk_idx, topk_w, y):
         # expert stand-in: de-quantised rows (reference test convention per_token_cast_back), made once, untimed
         y = (recv[0].float() * recv[1][:, None]).to(torch.bfloat16)
     out, _, _ = buf.combine(y, handle)
-    return out, n, y, recv, handle
+    return out, n, y, recv, handle, (per_rank, per_expert, is_in, lst)
 
 
 def one_step_nosync(buf, x, topk_idx, topk_w, y, worst):
@@ -140,6 +150,36 @@ def one_step_nosync(buf, x, topk_idx, topk_w, y, worst):
         y = (recv[0].float() * recv[1][:, None]).to(torch.bfloat16)      # expert stand-in, made once, untimed
     out, _, _ = buf.combine(y, handle)
     return out, y
+
+
+def step_outputs(step, rank, world):
+    """What one_step's caller receives, on the host as float32 / float64 (exact for every integer, INT8 and BF16 value): the layout
+    tables, the per-expert receive counts, the received rows' scales in full; of the received INT8 rows and the combined BF16 rows a
+    fixed sample of DUMP_ROWS / world rows, drawn with a seed per rank."""
+    import numpy as np
+
+    out, n, _, recv, _, (per_rank, per_expert, is_in, lst) = step
+    rng = np.random.default_rng(rank)
+
+    def rows(t):
+        idx = np.sort(rng.choice(t.shape[0], size=min(max(1, DUMP_ROWS // world), t.shape[0]), replace=False))
+        return t[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+
+    return {"num_tokens_per_rank": per_rank.cpu().numpy().astype(np.float64),
+            "num_tokens_per_expert": per_expert.cpu().numpy().astype(np.float64),
+            "is_token_in_rank": is_in.cpu().numpy().astype(np.float32),
+            "num_recv_tokens_per_expert": np.asarray(lst, dtype=np.float64),
+            "recv_x": rows(recv[0][:n]),
+            "recv_x_scales": recv[1][:n].float().cpu().numpy(),
+            "combined_x": rows(out)}
+
+
+def write_outputs(directory, arrays, rank, world):
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}_rank{rank}.npy" if world > 1 else f"{name}.npy"), a)
 
 
 def flush_c_stdout():
@@ -434,7 +474,7 @@ def cpu_baseline(sample_tokens):
     from oracle import ep as O
     from oracle.bf16 import f32_to_bf16_bits_rne
 
-    cores = os.cpu_count() or 8
+    cores = int(os.environ.get("OMP_NUM_THREADS") or 0) or len(os.sched_getaffinity(0))     # the CPUs this run may use, not the host's
     out = {}
     try:
         r = CA.timed_run(W=8, T=sample_tokens, H=HIDDEN, K=TOPK, E=EXPERTS, cores=cores, min_seconds=10.0, max_passes=8)
@@ -711,9 +751,10 @@ def fused_moe_section(buf, rank, world, T=4096):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def timed_steps(buf, x, topk_idx, topk_w, y, steps, warmup, profiled):
+def timed_steps(buf, x, topk_idx, topk_w, y, steps, warmup, profiled, on_last=None):
     """W warm-up steps, then exactly K timed steps between barrier + synchronize pairs; max over ranks.  The host collectives are
-    executed by every rank whether or not its own steps raised (see _phases); -> (seconds, profile dict, error or None)."""
+    executed by every rank whether or not its own steps raised (see _phases); -> (seconds, profile dict, error or None).
+    on_last(outputs of the last timed step) is called once the clock has stopped."""
     err = None
     try:
         for _ in range(warmup):
@@ -727,8 +768,9 @@ def timed_steps(buf, x, topk_idx, topk_w, y, steps, warmup, profiled):
     t0 = time.perf_counter()
     if err is None:
         try:
-            for _ in range(steps):
+            for _ in range(steps - 1):          # no step's outputs held across the next: the allocator sees what the hot path does
                 one_step(buf, x, topk_idx, topk_w, y)
+            last = one_step(buf, x, topk_idx, topk_w, y)
         except Exception as e:  # noqa: BLE001
             err = str(e)[:300]
     try:
@@ -736,6 +778,8 @@ def timed_steps(buf, x, topk_idx, topk_w, y, steps, warmup, profiled):
     except Exception as e:  # noqa: BLE001
         err = err or str(e)[:300]
     dt = time.perf_counter() - t0
+    if err is None and on_last is not None:
+        on_last(last)
     prof = {}
     if profiled:
         try:
@@ -767,7 +811,7 @@ def main():
     buf = deep_ep.Buffer(group, low_latency_mode=True, normal_strategy=strategy, low_latency_strategy=strategy)
     validated = None
     try:
-        out, n_recv, y, recv, handle = one_step(buf, x, topk_idx, topk_w, None)
+        out, n_recv, y, recv, handle, _ = one_step(buf, x, topk_idx, topk_w, None)
         torch.cuda.synchronize()
         validated = check_round_trip(out, x, topk_w) < 3e-3          # reference threshold for int8 (utils.py:198-203)
     except Exception as e:  # noqa: BLE001
@@ -780,7 +824,7 @@ def main():
     if int(flag.item()) == 0 and strategy != "alltoall":
         strategy = "alltoall"
         buf = deep_ep.Buffer(group, low_latency_mode=True, normal_strategy="alltoall", low_latency_strategy="alltoall")
-        out, n_recv, y, recv, handle = one_step(buf, x, topk_idx, topk_w, None)
+        out, n_recv, y, recv, handle, _ = one_step(buf, x, topk_idx, topk_w, None)
         torch.cuda.synchronize()
         validated = check_round_trip(out, x, topk_w) < 3e-3
     strategy = buf.normal_strategy.get_name()
@@ -790,14 +834,15 @@ def main():
     transports = [None]
     if windowed and hasattr(buf.runtime, "set_dispatch_transport"):
         transports = ["push", "pull"] if world > 1 else [buf.runtime.get_dispatch_transport()]
-    runs = {}
+    runs, last_outputs = {}, {}
     for tr in transports:
         if tr is not None:
             buf.runtime.set_dispatch_transport(tr)
+        keep = (lambda step, tr=tr: last_outputs.update({tr: step_outputs(step, rank, world)})) if args.dump_outputs else None
         # the timed region: exactly K steps, no instrumentation.  Kernel durations (roofline) come from a SECOND pass of the same
         # K steps with a HIP event pair around every kernel: each pair costs ~10 us of bubble at a kernel boundary (0.396 -> 0.448 ms
         # per step measured), which must not be charged to the hot path; that pass's own time is reported as profiled_ms_per_step.
-        dt, _, err = timed_steps(buf, x, topk_idx, topk_w, y, args.steps, args.warmup, False)
+        dt, _, err = timed_steps(buf, x, topk_idx, topk_w, y, args.steps, args.warmup, False, on_last=keep)
         prof, dt_prof = {}, None
         if err is None and windowed:
             dt_prof, prof, err = timed_steps(buf, x, topk_idx, topk_w, y, args.steps, 0, True)
@@ -810,6 +855,8 @@ def main():
     dt, prof, dt_prof = runs[best]
     if best is not None:
         buf.runtime.set_dispatch_transport(best)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, last_outputs[best], rank, world)
     rows = torch.tensor([n_recv], device="cuda", dtype=torch.float64)
     dist.all_reduce(rows, op=dist.ReduceOp.SUM)
     total_rows = float(rows.item())

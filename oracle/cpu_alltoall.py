@@ -98,6 +98,13 @@ def one_pass(x, topk_idx, topk_w, num_experts, group, quant=True):
     return out, recv, scale, lay
 
 
+def _host_barrier(group):
+    """dist.barrier() asks torch for the accelerator, which starts the GPU runtime in the calling process; these ranks compute on
+    the host only, and a rank that opens the GPU counts against the processes the GPU may serve.  A gloo all-reduce of a host
+    tensor synchronises the same way without touching the GPU."""
+    dist.all_reduce(torch.zeros(1), group=group)
+
+
 def _worker(rank, W, port, T, H, K, E, threads, min_seconds, max_passes, ret):
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     torch.set_num_threads(max(1, threads))
@@ -107,7 +114,7 @@ def _worker(rank, W, port, T, H, K, E, threads, min_seconds, max_passes, ret):
     topk_idx = torch.topk(torch.randn((T, E), generator=g).abs() + 1, K, dim=-1, sorted=False)[1]
     topk_w = torch.randn((T, K), generator=g)
     one_pass(x, topk_idx, topk_w, E, dist.group.WORLD)                                      # warm-up (connections, allocator)
-    dist.barrier()
+    _host_barrier(dist.group.WORLD)
     t0 = time.perf_counter()
     passes, rows = 0, 0
     while True:
@@ -118,7 +125,7 @@ def _worker(rank, W, port, T, H, K, E, threads, min_seconds, max_passes, ret):
         dist.all_reduce(stop, op=dist.ReduceOp.MAX)                                         # every rank stops after the same pass
         if stop.item() > 0:
             break
-    dist.barrier()
+    _host_barrier(dist.group.WORLD)
     dt = time.perf_counter() - t0
     tot = torch.tensor([float(rows)])
     dist.all_reduce(tot)
@@ -134,7 +141,7 @@ def timed_run(W=8, T=4096, H=7168, K=8, E=256, cores=None, min_seconds=10.0, max
 
     cores = cores or os.cpu_count() or W
     threads = max(1, cores // W)
-    mgr = mp.Manager()
+    mgr = mp.get_context("spawn").Manager()      # not forked: a fork of a caller that has opened the GPU inherits its device files
     ret = mgr.dict()
     mp.spawn(_worker, args=(W, port, T, H, K, E, threads, min_seconds, max_passes, ret), nprocs=W, join=True)
     out = dict(ret)

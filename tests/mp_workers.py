@@ -42,6 +42,17 @@ def _set_device(rank):
     return dev
 
 
+# Processes one GPU may serve at once on the nodes the suite runs on, the pytest process that spawns the ranks included (it has
+# cuda:0 open).  A node without that cap may raise it to run the eight-rank cases on one GPU.
+MAX_PROCS_PER_GPU = int(os.environ.get("MI_TEST_MAX_PROCS_PER_GPU", "6"))
+
+
+def ranks_on_first_gpu(world):
+    """How many of `world` ranks _set_device places on cuda:0."""
+    n = torch.cuda.device_count()
+    return -(-world // n) if (os.environ.get("MI_TEST_DEVICE_PER_RANK") == "1" and n > 1) else world
+
+
 def _init(rank, world, port, backend="gloo"):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)

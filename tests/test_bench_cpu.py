@@ -4,6 +4,8 @@ import importlib.util
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -16,7 +18,7 @@ def _bench():
 
 def _args(**kw):
     d = dict(gpus=1, steps=30, warmup=5, tokens=4096, strategy="default", no_cpu_baseline=False, no_mla=False, no_extra=False,
-             dry_run_8=False)
+             dry_run_8=False, dump_outputs=None)
     d.update(kw)
     return argparse.Namespace(**d)
 
@@ -35,7 +37,9 @@ def test_self_launch_decision():
     assert tail[:6] == ["--gpus", "8", "--steps", "7", "--warmup", "2"] and "--no-extra" in tail and "--dry-run-8" not in tail
     assert env["HSA_ENABLE_IPC_MODE_LEGACY"] == "0" and "BENCH_SINGLE_DEVICE" not in env and env["PATH"] == "/usr/bin"
     cmd, env = B.self_launch_command(_args(gpus=2), {})
-    assert cmd[cmd.index("--nproc-per-node") + 1] == "2" and cmd[cmd.index("--gpus") + 1] == "2"
+    assert cmd[cmd.index("--nproc-per-node") + 1] == "2" and cmd[cmd.index("--gpus") + 1] == "2" and "--dump-outputs" not in cmd
+    cmd, env = B.self_launch_command(_args(gpus=2, dump_outputs="out"), {})
+    assert cmd[cmd.index("--dump-outputs") + 1] == os.path.abspath("out")
     # --dry-run-8: the same re-execution with every rank on cuda:0
     cmd, env = B.self_launch_command(_args(dry_run_8=True), {})
     assert env["BENCH_SINGLE_DEVICE"] == "1" and "--dry-run-8" in cmd and cmd[cmd.index("--gpus") + 1] == "8"
@@ -44,9 +48,49 @@ def test_self_launch_decision():
     try:
         sys.argv = ["bench.py"] + tail
         a = B.parse()
-        assert a.gpus == 8 and a.steps == 7 and a.warmup == 2 and a.no_extra
+        assert a.gpus == 8 and a.steps == 7 and a.warmup == 2 and a.no_extra and a.dump_outputs is None
     finally:
         sys.argv = sys_argv
+
+
+def test_step_count_is_validated(monkeypatch, capsys):
+    B = _bench()
+    for argv in (["--steps", "0"], ["--warmup", "-1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit):
+            B.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "1", "--warmup", "0", "--dump-outputs", "d"])
+    a = B.parse()
+    assert (a.steps, a.warmup, a.dump_outputs) == (1, 0, "d")
+
+
+def test_dumped_step_outputs(tmp_path):
+    """--dump-outputs: every array one_step returns to its caller, float32 / float64 and exact, the [rows, hidden] ones as a fixed
+    seeded row sample; at N > 1 a file per rank."""
+    import numpy as np
+    import torch
+    B = _bench()
+    T, H, W, E, n = 300, 16, 2, 8, 700
+    recv_x = torch.randint(-128, 128, (n, H), dtype=torch.int8)
+    scales = torch.rand(n)
+    out = torch.randn(T, H).to(torch.bfloat16)
+    layout = (torch.tensor([T, 250]), torch.arange(E), torch.rand(T, W) > 0.5, [n // E] * E)
+    step = (out, n, None, (recv_x, scales), None, layout)
+    a = B.step_outputs(step, rank=1, world=W)
+    assert set(a) == {"num_tokens_per_rank", "num_tokens_per_expert", "is_token_in_rank", "num_recv_tokens_per_expert", "recv_x",
+                      "recv_x_scales", "combined_x"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    k = B.DUMP_ROWS // W
+    assert a["recv_x"].shape == (k, H) and a["combined_x"].shape == (k, H) and a["recv_x_scales"].shape == (n,)
+    rows = [int(np.flatnonzero((recv_x.float().numpy() == r).all(1))[0]) for r in a["recv_x"]]
+    assert rows == sorted(rows) and len(set(rows)) == k                  # distinct rows, in receive order, exact values
+    assert np.array_equal(a["is_token_in_rank"], layout[2].numpy().astype(np.float32))
+    b = B.step_outputs(step, rank=1, world=W)                            # the same sample every time
+    assert all(np.array_equal(a[x], b[x]) for x in a)
+    B.write_outputs(str(tmp_path), a, 1, W)
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{x}_rank1.npy" for x in a)
+    B.write_outputs(str(tmp_path / "one"), a, 0, 1)
+    assert np.array_equal(np.load(tmp_path / "one" / "combined_x.npy"), a["combined_x"])
 
 
 def test_xgmi_projection_arithmetic():

@@ -46,9 +46,9 @@ def test_bench_two_ranks_one_gpu():
 
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
-def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-mla"], cwd=ROOT,
-                       capture_output=True, text=True, timeout=540)
+def test_bench_single_gpu_line(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-mla",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     for k in REQUIRED + ("roofline", "cpu_baseline", "low_latency", "fused_deep_moe"):
@@ -66,6 +66,15 @@ def test_bench_single_gpu_line():
     xp = d["xgmi_projection"]
     assert xp["ep"] == 8 and xp["peak_GBps"] == 7 * 153.0 and set(xp["legs"]) == {"dispatch_push", "combine_push"}
     assert xp["legs"]["combine_push"]["cross_gpu_bytes"] > 3.5e8 and xp["projected_step_ms"] > xp["link_bound_floor_ms"] > 0.3
+    # --dump-outputs: the last timed step's outputs, float32 / float64, within 64 MB; the sampled combined rows are the round trip's
+    import numpy as np
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {"num_tokens_per_rank", "num_tokens_per_expert", "is_token_in_rank", "num_recv_tokens_per_expert", "recv_x",
+                        "recv_x_scales", "combined_x"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    n = int(got["num_recv_tokens_per_expert"].sum())
+    assert got["num_tokens_per_rank"].tolist() == [4096] and got["recv_x_scales"].shape == (n,)
+    assert got["recv_x"].shape == (512, 7168) and got["combined_x"].shape == (512, 7168) and np.isfinite(got["combined_x"]).all()
 
 
 @pytest.mark.gpu
@@ -73,6 +82,9 @@ def test_bench_single_gpu_line():
 def test_bench_dry_run_eight_ranks_one_gpu():
     """`bench.py --dry-run-8`: the 8-GPU launch line on ONE GPU at full C2 size (every rank on cuda:0, hipIpc windows): every key a real
     8-GPU line carries must be there -- both transports, per-leg and per-link xGMI pricing, C3 and C5 sections validated."""
+    import mp_workers
+    if 8 + 1 > mp_workers.MAX_PROCS_PER_GPU:          # eight ranks and this process, all on cuda:0
+        pytest.skip(f"needs a GPU that 9 processes may share, at most {mp_workers.MAX_PROCS_PER_GPU} may share one here")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run-8", "--steps", "2", "--warmup", "1"], cwd=ROOT,
                        capture_output=True, text=True, timeout=840)
     assert r.returncode == 0, r.stderr[-3000:]

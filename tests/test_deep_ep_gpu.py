@@ -1,11 +1,21 @@
 """GPU tests of the full boundary: deep_ep.Buffer -> deep_ep_cpp (C++ runtime) -> HIP kernels, with W ranks as W
 processes sharing ONE GPU and their windows mapped through hipIpc (the same code path 8 GPUs take over xGMI)."""
 import pytest
+import torch
 
 import mp_workers
-from test_deep_ep_plumbing_cpu import _spawn
+from test_deep_ep_plumbing_cpu import _spawn as _spawn_ranks
 
 pytestmark = pytest.mark.gpu
+
+
+def _spawn(fn, world, cfg):
+    """_spawn_ranks, skipped up front when cuda:0 cannot take the ranks placed on it next to this process."""
+    procs = mp_workers.ranks_on_first_gpu(world) + 1
+    if procs > mp_workers.MAX_PROCS_PER_GPU:
+        pytest.skip(f"needs {world} GPUs with MI_TEST_DEVICE_PER_RANK=1, found {torch.cuda.device_count()}: {world} ranks on one GPU "
+                    f"make {procs} processes on it, at most {mp_workers.MAX_PROCS_PER_GPU} may share a GPU")
+    _spawn_ranks(fn, world, cfg)
 
 
 @pytest.mark.parametrize("cfg", [

@@ -76,8 +76,6 @@ def test_add_rmsnorm_bias(B, H, dtype):
 @pytest.mark.parametrize("hd,qh,kvh,B", [(128, 6144, 1024, 12), (64, 512, 128, 3), (256, 1024, 256, 5)])
 def test_split_qkv_rmsnorm_rope(rope_dim, neox, norm, bias, hd, qh, kvh, B):
     from sgl_kernel_npu.norm.split_qkv_rmsnorm_rope import split_qkv_rmsnorm_rope
-    if rope_dim > hd:
-        pytest.skip("rope_dim > head_dim")
     rng = np.random.default_rng(0)
     torch.manual_seed(0)
     qkv = torch.randn(B, qh + 2 * kvh).to(torch.bfloat16)
@@ -86,6 +84,11 @@ def test_split_qkv_rmsnorm_rope(rope_dim, neox, norm, bias, hd, qh, kvh, B):
     cos = torch.from_numpy(rng.uniform(0, 1, [B, 1, 1, rope_dim])).to(torch.bfloat16)
     kwargs = dict(eps=1e-6 if norm else None, q_weight=qw if norm else None, k_weight=kw if norm else None,
                   q_bias=qb if (norm and bias) else None, k_bias=kb if (norm and bias) else None, is_neox_style=neox)
+    if rope_dim > hd:          # a rotary part wider than the head: refused before any launch
+        dev = {k: (v.cuda() if isinstance(v, torch.Tensor) else v) for k, v in kwargs.items()}
+        with pytest.raises(RuntimeError):
+            split_qkv_rmsnorm_rope(qkv.cuda(), sin.cuda(), cos.cuda(), qh, kvh, hd, **dev)
+        return
     wq, wk, wv = OK.split_qkv_rmsnorm_rope(qkv, sin, cos, qh, kvh, hd, **kwargs)
     dev = {k: (v.cuda() if isinstance(v, torch.Tensor) else v) for k, v in kwargs.items()}
     q, k, v = split_qkv_rmsnorm_rope(qkv.cuda(), sin.cuda(), cos.cuda(), qh, kvh, hd, **dev)

@@ -162,10 +162,10 @@ def test_non_finite_rows_quantise_as_the_oracle_says(mode, eps):
         want = O.normal_dispatch(xs, idxs, E, True)
         rows = lambda g, w: (g["recv_x"], g["recv_x_scales"], g["recv_src_idx"], w.recv_x, w.recv_x_scales, w.total_recv)
     else:
-        if mode != "replicated":
-            pytest.skip("one low-latency form")
+        # low-latency dispatch: "compact" takes the one-launch layout + send form, "push" the separate send launch, "replicated" either
         h = Hh.InProcEP(W, E, T, K, H)
-        got = h.ll_dispatch([dev_bf16(x) for x in xs], [torch.from_numpy(i).int().cuda() for i in idxs], Hh.QUANT_INT8_NOEPS, 1)
+        fused = {"replicated": None, "compact": True, "push": False}[mode]
+        got = h.ll_dispatch([dev_bf16(x) for x in xs], [torch.from_numpy(i).int().cuda() for i in idxs], Hh.QUANT_INT8_NOEPS, 1, fused=fused)
         want = O.low_latency_dispatch(xs, idxs, T, E, True)
         rows = lambda g, w: (g["packed_recv_x"], g["packed_recv_x_scales"], g["src_info"], w.packed_recv_x, w.packed_recv_x_scales, w.total)
     seen = 0
