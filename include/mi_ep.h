@@ -266,6 +266,16 @@ int mi_ep_dispatch_pull_local(const void *my_rows, const void *topk_idx, int idx
                               int hidden, int num_experts, int num_ranks, int my_rank, int quant_mode, int rows_hint, void *recv_x,
                               float *recv_x_scales, int32_t *recv_src_idx, int32_t *local_row_out, const uint64_t *epoch_ctr,
                               size_t parity_stride, void *stream);
+/* num_ranks == 1 only: stage + pull_local in one launch, without the staged rows.  Token t's row is read from x, quantised in registers
+ * by the code mi_ep_dispatch_stage uses (all four quant modes) and stored straight to each valid selection (t, k), at output row
+ * recv_count[e] - num_tokens_per_expert[e] + send_token_idx_small[t, k] (rows < rows_hint only), with its scale, the triple (0, t, k)
+ * and local_row_out[t * K + k] -- byte for byte what mi_ep_dispatch_stage_compact + mi_ep_dispatch_pull_local produce at one rank.
+ * recv_count = the notify exchange's inclusive cumsum; the notify still runs, only the staging launch is skipped.  Reads x and the
+ * tables only, so a second call (larger rows_hint) simply writes the rows again. */
+int mi_ep_dispatch_stage_local(const void *x, const void *topk_idx, int idx_is_i32, const int32_t *send_token_idx_small,
+                               const int32_t *recv_count, const int32_t *num_tokens_per_expert, int num_tokens, int num_topk,
+                               int hidden, int num_experts, int quant_mode, int rows_hint, void *recv_x, float *recv_x_scales,
+                               int32_t *recv_src_idx, int32_t *local_row_out, void *stream);
 
 /* Push transport of normal dispatch (selectable next to the pull above; the same received bytes).  The sender writes the
  * quantised row of token t ONCE into the window of every rank that owns at least one of the token's experts (the reference

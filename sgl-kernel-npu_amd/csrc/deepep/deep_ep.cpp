@@ -477,9 +477,10 @@ void Buffer::clean_low_latency_buffer(int, int, int) {}   // no-op, as in the re
 // stage (push: into the destination ranks' windows; pull: into the own window) -> ONE single-workgroup launch that posts
 // this rank's counts + "rows staged" flag, collects everybody's and derives the tables.  The call's epoch and ping-pong
 // half come from the device-resident counter of the family (see include/mi_ep.h), so nothing here depends on how many
-// calls ran before.
+// calls ran before.  stage_local (num_ranks == 1 only): no staging launch -- dispatch_pull then quantises x straight into the
+// receive rows (mi_ep_dispatch_stage_local); the notify exchange still runs, its tables and the host summary are needed either way.
 Buffer::DispatchExchange Buffer::dispatch_exchange(const at::Tensor &x, const at::Tensor &topk_idx, const Layout &lay, int E, int qm,
-                                                   bool want_summary, int32_t *wait_stats, hipStream_t st)
+                                                   bool want_summary, int32_t *wait_stats, hipStream_t st, bool stage_local)
 {
     const int T = (int)x.size(0), H = (int)x.size(1), K = (int)topk_idx.size(1), W = (int)num_ranks, L = E / W;
     const size_t rb = mi_ep_dispatch_row_bytes(H, qm);
@@ -498,7 +499,9 @@ Buffer::DispatchExchange Buffer::dispatch_exchange(const at::Tensor &x, const at
     uint64_t *ctr = epoch_ctr(kDispatch);
     auto region_peers = peer_family_bases(kDispatch);
     const bool i32idx = topk_idx.scalar_type() == at::kInt;
-    { ProfScope ps_(this, ex.push ? "dispatch_stage_push" : "dispatch_stage", st);
+    EP_HOST_ASSERT(!stage_local || W == 1);
+    ex.stage_local = stage_local;
+    if (!stage_local) { ProfScope ps_(this, ex.push ? "dispatch_stage_push" : "dispatch_stage", st);
       if (ex.push)
           MI_EP_CHECK(mi_ep_dispatch_stage_push(x.data_ptr(), topk_idx.data_ptr(), i32idx, lay.send_token_idx_small.data_ptr<int>(),
                                                 lay.send_data_offset.data_ptr<int>(), T, K, H, E, W, (int)rank, qm,
@@ -531,6 +534,7 @@ Buffer::DispatchExchange Buffer::dispatch_exchange(const at::Tensor &x, const at
     if (ex.push)
         for (int s = 0; s < W; ++s) ex.src_bases[(size_t)s] = family_base(kDispatch) + (size_t)s * ex.slab_bytes;
     ex.topk_idx = topk_idx, ex.send_token_idx_small = lay.send_token_idx_small, ex.num_tokens_per_expert = lay.num_tokens_per_expert;
+    if (stage_local) ex.x = x;
     ex.num_tokens = T, ex.num_experts = E;
     return ex;
 }
@@ -544,7 +548,7 @@ void Buffer::dispatch_pull(const DispatchExchange &ex, int H, int K, int L, int 
     rx = quant ? at::empty({rows_alloc, H}, at::dtype(payload_dtype(qm)).device(dev)) : at::empty({rows_alloc, H}, x_opts);
     rs = at::empty({rows_alloc}, at::dtype(at::kFloat).device(dev));
     src_idx = at::empty({rows_alloc * 3}, at::dtype(at::kInt).device(dev));
-    ProfScope ps_(this, "dispatch_pull", st);
+    ProfScope ps_(this, ex.stage_local ? "dispatch_stage_local" : "dispatch_pull", st);
     // this rank's own tokens are gathered token by token (their staged row is read once, not once per selection); everybody else's
     // rows row by row.  MI_EP_DISPATCH_LOCAL=0: every row through pull_indexed.
     const bool local = dispatch_local_rows;
@@ -554,7 +558,13 @@ void Buffer::dispatch_pull(const DispatchExchange &ex, int H, int K, int L, int 
     at::Tensor local_row_out;
     if (local && num_ranks == 1 && combine_local_rows_enabled && ex.num_tokens > 0)
         local_row_out = at::empty({(int64_t)ex.num_tokens * K}, at::dtype(at::kInt).device(dev));
-    if (local && ex.num_tokens > 0)
+    if (ex.stage_local && ex.num_tokens > 0)        // (reads x and the tables only: a second, exact-size call writes the same rows again)
+        MI_EP_CHECK(mi_ep_dispatch_stage_local(ex.x.data_ptr(), ex.topk_idx.data_ptr(), ex.topk_idx.scalar_type() == at::kInt,
+                                               ex.send_token_idx_small.data_ptr<int>(), ex.nt.recv_count.data_ptr<int>(),
+                                               ex.num_tokens_per_expert.data_ptr<int>(), ex.num_tokens, K, H, ex.num_experts, qm,
+                                               (int)rows_alloc, rx.data_ptr(), quant ? rs.data_ptr<float>() : nullptr, src_idx.data_ptr<int>(),
+                                               local_row_out.defined() ? local_row_out.data_ptr<int>() : nullptr, st));
+    else if (local && ex.num_tokens > 0)
         MI_EP_CHECK(mi_ep_dispatch_pull_local(ex.src_bases[(size_t)rank], ex.topk_idx.data_ptr(), ex.topk_idx.scalar_type() == at::kInt,
                                               ex.send_token_idx_small.data_ptr<int>(), ex.nt.recv_count.data_ptr<int>(),
                                               ex.num_tokens_per_expert.data_ptr<int>(), ex.num_tokens, K, H, ex.num_experts, (int)num_ranks,
@@ -624,7 +634,9 @@ Buffer::intranode_dispatch(const at::Tensor &x, const std::optional<at::Tensor> 
         wait_stats = dispatch_wait_recv_cost_stats->data_ptr<int>();
     }
     const bool host_sync = num_worst_tokens <= 0;
-    DispatchExchange ex = dispatch_exchange(x, *topk_idx, lay, E, qm, host_sync, wait_stats, st);
+    // one rank, own rows gathered token-wise: nobody else reads the staged rows, so the pull quantises x itself (no staging launch)
+    const bool stage_local = W == 1 && dispatch_local_rows && dispatch_stage_local;
+    DispatchExchange ex = dispatch_exchange(x, *topk_idx, lay, E, qm, host_sync, wait_stats, st, stage_local);
 
     // Receive buffers + the pull launch.  The exact row count reaches the host only through the pinned summary word;
     // to keep the GPU busy across that round trip the pull is launched FIRST into buffers sized from the previous call

@@ -49,6 +49,11 @@ public:
     void set_dispatch_transport(const std::string &name);
     void set_local_row_paths(bool dispatch_local, bool combine_local);
     std::vector<bool> get_local_row_paths() const { return {dispatch_local_rows, combine_local_rows_enabled}; }
+    // MI355X only: at num_ranks == 1 with the own-row dispatch path on, the staging launch is skipped and the pull is
+    // mi_ep_dispatch_stage_local (x quantised straight into the receive rows); default from MI_EP_DISPATCH_STAGE_LOCAL (0 = stage +
+    // pull_local).  Results are identical either way.
+    void set_dispatch_stage_local(bool on) { dispatch_stage_local = on; }
+    bool get_dispatch_stage_local() const { return dispatch_stage_local; }
     // MI355X only: fused_deep_moe / dispatch_ffn_combine at prefill sizes multiply the staged token rows in place (a row-offset table) instead
     // of a K-fold gathered copy; default from MI_EP_FUSED_GATHER (0 = gather).  Results are identical either way.
     // MI355X only: GEMM1 of fused_deep_moe / dispatch_ffn_combine requantises its rows in its epilogue (mi_ep_moe_gemm1_swiglu_quant) instead
@@ -266,10 +271,13 @@ private:
         bool push = false;
         // what the token-wise gather of this rank's own rows needs (mi_ep_dispatch_pull_local)
         at::Tensor topk_idx, send_token_idx_small, num_tokens_per_expert;
+        // stage_local: nothing was staged; the pull reads the token rows from x (mi_ep_dispatch_stage_local)
+        at::Tensor x;
+        bool stage_local = false;
         int num_tokens = 0, num_experts = 0;
     };
     DispatchExchange dispatch_exchange(const at::Tensor &x, const at::Tensor &topk_idx, const Layout &lay, int E, int qm,
-                                       bool want_summary, int32_t *wait_stats, hipStream_t st);
+                                       bool want_summary, int32_t *wait_stats, hipStream_t st, bool stage_local = false);
     void dispatch_pull(const DispatchExchange &ex, int H, int K, int L, int qm, int64_t rows_alloc, const at::TensorOptions &x_opts,
                        at::Tensor &rx, at::Tensor &rs, at::Tensor &src_idx, hipStream_t st);
     at::Tensor combine_finish(const at::Tensor &topk_idx, const float *topk_weights, int H, int E, const at::TensorOptions &opts,
@@ -302,6 +310,7 @@ private:
     // defaults from MI_EP_DISPATCH_LOCAL / MI_EP_COMBINE_LOCAL (0 = off), see set_local_row_paths()
     bool dispatch_local_rows = !(getenv("MI_EP_DISPATCH_LOCAL") && atoi(getenv("MI_EP_DISPATCH_LOCAL")) == 0);
     bool combine_local_rows_enabled = !(getenv("MI_EP_COMBINE_LOCAL") && atoi(getenv("MI_EP_COMBINE_LOCAL")) == 0);
+    bool dispatch_stage_local = !(getenv("MI_EP_DISPATCH_STAGE_LOCAL") && atoi(getenv("MI_EP_DISPATCH_STAGE_LOCAL")) == 0);
     bool fused_rows_in_place = !(getenv("MI_EP_FUSED_GATHER") && atoi(getenv("MI_EP_FUSED_GATHER")) == 0);
     bool fused_requant = getenv("MI_EP_FUSED_REQUANT") && atoi(getenv("MI_EP_FUSED_REQUANT")) != 0;
     int gemm_xcds = 1;

@@ -131,24 +131,12 @@ __device__ __forceinline__ void route_token(const LLGeom &ll, const void *topk_i
 // ---------------------------------------------------------------------------------------------
 // stage, INT8: item = 16 consecutive elements = two 16-B loads -> one 16-B store
 // ---------------------------------------------------------------------------------------------
-// QM = MI_EP_QUANT_INT8 / MI_EP_QUANT_INT8_NOEPS / MI_EP_QUANT_FP8_E4M3 (one byte per element each, same row layout)
-template <bool I32, int QM, bool LATE>
-__device__ __forceinline__ void stage_int8_body(
-    const uint16_t *__restrict__ x, const void *__restrict__ topk_idx, const int32_t *__restrict__ idx_small,
-    const int32_t *__restrict__ send_off, int T, int K, int H, int E, int my_rank, const PeerPtrs &dsts, const LLGeom &ll, int ksplit,
-    size_t idx_off, const PushGeom &pg, const Parity &par, const int wid, const LateIdx &late)
+// Row load and quantisation, shared by every kernel that quantises a token row (stage_int8_body, stage_local_kernel): the rounding
+// exists once.  Item it * kWave + lane of row t; items past H / 16 are zero (they take part in the maximum).
+__device__ __forceinline__ void ld_row_items(const uint16_t *__restrict__ x, int t, int H, u32x4 (&raw)[kMaxItems][2])
 {
-    const int lane = lane_id();
-    // ksplit waves share a token (decode-size batches: every wave re-reads the row from L2 and writes K / ksplit copies)
-    const int t = wid / ksplit, kpart = wid - t * ksplit;
-    if (t >= T) return;
-    const int nitems = H / 16;
-    const size_t stride = MI_EP_ROW_STRIDE(H);
-    // the row is requested before the routing is known (a token that selects nothing is the rare case): behind the routing's two
-    // dependent loads (expert id, then slot and segment offset) the 14 KB of the row started one to two round trips late
+    const int lane = lane_id(), nitems = H / 16;
     const u32x4 *src = (const u32x4 *)(x + (size_t)t * H);
-    u32x4 raw[kMaxItems][2];
-    float amax = 0.f;
 #pragma unroll
     for (int it = 0; it < kMaxItems; ++it) {
         const int item = it * kWave + lane;
@@ -159,16 +147,13 @@ __device__ __forceinline__ void stage_int8_body(
             raw[it][0] = raw[it][1] = u32x4{0, 0, 0, 0};
         }
     }
-    // routing of this token: lane k < K owns pair (t,k)
-    long long e_l = -1;
-    int slot_l = 0, dst_l = 0;
-    if (lane < K) {
-        e_l = ld_idx<I32>(topk_idx, (long long)t * K + lane);
-        if (e_l < 0 || e_l >= E) e_l = -1;
-    }
-    if (!LATE) route_token<I32, false>(ll, topk_idx, idx_small, send_off, t, K, E, my_rank, late, e_l, slot_l, dst_l);
-    const unsigned long long vmask = __ballot(e_l >= 0);
-    if (vmask == 0ull) return;      // token selects nothing: no row is produced
+}
+// QM = MI_EP_QUANT_INT8 / MI_EP_QUANT_INT8_NOEPS / MI_EP_QUANT_FP8_E4M3 (one byte per element each, same row layout): the row's |max|
+// (whole wave), the per-token scale the receiver multiplies by, and the quantised items
+template <int QM>
+__device__ __forceinline__ void quant_row(u32x4 (&raw)[kMaxItems][2], u32x4 (&q)[kMaxItems], float &scale_out)
+{
+    float amax = 0.f;
     // |x| of a bf16 orders like its bit pattern as an unsigned 16-bit integer, so the row maximum is taken on the packed words
     // (v_pk_max_u16, two elements per instruction, no unpacking): the SIMDs are 16 lanes wide, every wave instruction costs 4 cycles,
     // and this kernel spent as long in its ~1260 VALU instructions per token as in its memory phases
@@ -187,7 +172,7 @@ __device__ __forceinline__ void stage_int8_body(
         amax = __uint_as_float((m > 0x7F80u ? 0x7F80u : m) << 16);
     }
     amax = wave_max(amax);
-    float s, scale_out;
+    float s;
     if (QM == MI_EP_QUANT_INT8) {
         s = 127.0f / (amax + 1e-12f);
         scale_out = 1.0f / s;
@@ -198,7 +183,6 @@ __device__ __forceinline__ void stage_int8_body(
         s = amax > 0.f ? 448.0f / amax : 1.0f;
         scale_out = 1.0f / s;
     }
-    u32x4 q[kMaxItems];
     // the raw row is made opaque between the two passes: otherwise the compiler keeps the 128 floats it unpacked for the maximum alive
     // for the quantisation (161 VGPRs, 3 waves per SIMD -- the 4096 token waves of a C2 batch then need two rounds); unpacking again
     // costs one shift / mask per element
@@ -234,6 +218,36 @@ __device__ __forceinline__ void stage_int8_body(
                 q[it][h * 2 + jj] = p0 | p1;
             }
     }
+}
+template <bool I32, int QM, bool LATE>
+__device__ __forceinline__ void stage_int8_body(
+    const uint16_t *__restrict__ x, const void *__restrict__ topk_idx, const int32_t *__restrict__ idx_small,
+    const int32_t *__restrict__ send_off, int T, int K, int H, int E, int my_rank, const PeerPtrs &dsts, const LLGeom &ll, int ksplit,
+    size_t idx_off, const PushGeom &pg, const Parity &par, const int wid, const LateIdx &late)
+{
+    const int lane = lane_id();
+    // ksplit waves share a token (decode-size batches: every wave re-reads the row from L2 and writes K / ksplit copies)
+    const int t = wid / ksplit, kpart = wid - t * ksplit;
+    if (t >= T) return;
+    const int nitems = H / 16;
+    const size_t stride = MI_EP_ROW_STRIDE(H);
+    // the row is requested before the routing is known (a token that selects nothing is the rare case): behind the routing's two
+    // dependent loads (expert id, then slot and segment offset) the 14 KB of the row started one to two round trips late
+    u32x4 raw[kMaxItems][2];
+    ld_row_items(x, t, H, raw);
+    // routing of this token: lane k < K owns pair (t,k)
+    long long e_l = -1;
+    int slot_l = 0, dst_l = 0;
+    if (lane < K) {
+        e_l = ld_idx<I32>(topk_idx, (long long)t * K + lane);
+        if (e_l < 0 || e_l >= E) e_l = -1;
+    }
+    if (!LATE) route_token<I32, false>(ll, topk_idx, idx_small, send_off, t, K, E, my_rank, late, e_l, slot_l, dst_l);
+    const unsigned long long vmask = __ballot(e_l >= 0);
+    if (vmask == 0ull) return;      // token selects nothing: no row is produced
+    float scale_out;
+    u32x4 q[kMaxItems];
+    quant_row<QM>(raw, q, scale_out);
     if (LATE) route_token<I32, true>(ll, topk_idx, idx_small, send_off, t, K, E, my_rank, late, e_l, slot_l, dst_l);
     if (idx_off) {
         // compact staging (normal-mode pull transport): the row is written ONCE at slot t; the expert-sorted index tells the
@@ -296,6 +310,18 @@ __global__ __launch_bounds__(kWave * kStageWaves) void stage_int8_kernel(
 }
 
 // stage, BF16 (no quantisation): item = one 16-B chunk
+constexpr int kChunkItems = kMaxItems * 2;      // 16-B chunks per lane (16)
+// chunk it * kWave + lane of row t (shared with stage_local_kernel); chunks past H / 8 are left unset and never stored
+__device__ __forceinline__ void ld_row_chunks(const uint16_t *__restrict__ x, int t, int H, u32x4 (&raw)[kChunkItems])
+{
+    const int lane = lane_id(), nitems = H / 8;
+    const u32x4 *src = (const u32x4 *)(x + (size_t)t * H);
+#pragma unroll
+    for (int it = 0; it < kChunkItems; ++it) {
+        const int item = it * kWave + lane;
+        if (item < nitems) raw[it] = src[item];
+    }
+}
 template <bool I32, bool LATE>
 __device__ __forceinline__ void stage_bf16_body(
     const uint16_t *__restrict__ x, const void *__restrict__ topk_idx, const int32_t *__restrict__ idx_small,
@@ -317,14 +343,9 @@ __device__ __forceinline__ void stage_bf16_body(
     if (!LATE) route_token<I32, false>(ll, topk_idx, idx_small, send_off, t, K, E, my_rank, late, e_l, slot_l, dst_l);
     const unsigned long long vmask = __ballot(e_l >= 0);
     if (vmask == 0ull) return;
-    const u32x4 *src = (const u32x4 *)(x + (size_t)t * H);
-    constexpr int kIt = kMaxItems * 2;
+    constexpr int kIt = kChunkItems;
     u32x4 raw[kIt];
-#pragma unroll
-    for (int it = 0; it < kIt; ++it) {
-        const int item = it * kWave + lane;
-        if (item < nitems) raw[it] = src[item];
-    }
+    ld_row_chunks(x, t, H, raw);
     if (LATE) route_token<I32, true>(ll, topk_idx, idx_small, send_off, t, K, E, my_rank, late, e_l, slot_l, dst_l);
     if (idx_off) {                                  // compact / push staging, see stage_int8_kernel
         stage_token_rows(pg, dsts, parity_off(par), idx_off, my_rank, t, K, e_l, slot_l, send_off, [&](uint8_t *base) {
@@ -904,6 +925,70 @@ __global__ __launch_bounds__(kWave * kPullWaves) void pull_local_kernel(
     }
 }
 
+// Single-rank dispatch in one pass (mi_ep_dispatch_stage_local): the token row is read from x, quantised in registers by the same
+// code as stage_int8_body (ld_row_items + quant_row; bf16: ld_row_chunks, a plain copy) and stored straight to each of its selections'
+// receive rows, with the scale and (0, t, k) triple -- the bytes stage_compact + pull_local_kernel produce at num_ranks == 1, without
+// the staged row in between (T * (H + 16) bytes written, then read back, and one launch).  Output row of selection (t, k):
+// recv_count[e] - num_tokens_per_expert[e] + send_token_idx_small[t, k]; rows below row_capacity only; the write-back / nontemporal
+// split of pull_local_kernel (pull_nt_from_row).  One wave per token, kStageWaves tokens per workgroup.
+template <bool I32, int QM, bool NT>
+__global__ __launch_bounds__(kWave * kStageWaves) void stage_local_kernel(
+    const uint16_t *__restrict__ x, const void *__restrict__ topk_idx, const int32_t *__restrict__ idx_small,
+    const int32_t *__restrict__ recv_count, const int32_t *__restrict__ tokens_per_expert, int T, int K, int H, int E,
+    uint8_t *__restrict__ recv_x, float *__restrict__ recv_scales, int32_t *__restrict__ recv_src_idx, int row_capacity,
+    int nt_from_row, int32_t *__restrict__ local_row_out)
+{
+    constexpr bool kQuant = QM != MI_EP_QUANT_NONE;
+    constexpr int kIt = kQuant ? kMaxItems : kChunkItems;
+    const int lane = lane_id();
+    const int t = __builtin_amdgcn_readfirstlane(blockIdx.x * kStageWaves + threadIdx.x / kWave);
+    if (t >= T) return;
+    // the row is requested before the routing is known (its three dependent loads run under the row's latency)
+    u32x4 raw[kQuant ? kMaxItems : 1][2];
+    u32x4 q[kIt];
+    if constexpr (kQuant) ld_row_items(x, t, H, raw);
+    else ld_row_chunks(x, t, H, q);
+    int r_l = -1;
+    if (lane < K) {
+        const long long e = ld_idx<I32>(topk_idx, (long long)t * K + lane);
+        if (e >= 0 && e < E) {
+            const int r = recv_count[e] - tokens_per_expert[e] + idx_small[(long long)t * K + lane];
+            if (r >= 0 && r < row_capacity) r_l = r;
+        }
+    }
+    const unsigned long long lmask = __ballot(r_l >= 0);
+    if (lmask == 0ull) return;                                    // token selects nothing: no row is produced
+    float scale = 0.f;                                            // bf16 rows: the staged meta's scale word is 0 as well
+    if constexpr (kQuant) quant_row<QM>(raw, q, scale);
+    const int n16 = kQuant ? H / 16 : H / 8;
+    const size_t payload = kQuant ? (size_t)H : (size_t)H * 2;
+    for (unsigned long long m = lmask; m; m &= m - 1) {           // wave-uniform walk over the token's selections
+        const int k = __builtin_ctzll(m);
+        const int rk = __builtin_amdgcn_readlane(r_l, k);
+        u32x4 *d16 = (u32x4 *)(recv_x + (size_t)rk * payload);
+        if (NT && rk >= nt_from_row) {
+#pragma unroll
+            for (int it = 0; it < kIt; ++it) {
+                const int item = it * kWave + lane;
+                if (item < n16) st_row<true>(d16 + item, q[it]);
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < kIt; ++it) {
+                const int item = it * kWave + lane;
+                if (item < n16) st_row<false>(d16 + item, q[it]);
+            }
+        }
+    }
+    if (r_l >= 0) {                                               // lane k writes the meta of selection k
+        if (recv_scales) recv_scales[r_l] = scale;
+        recv_src_idx[(size_t)r_l * 3 + 0] = 0;
+        recv_src_idx[(size_t)r_l * 3 + 1] = t;
+        recv_src_idx[(size_t)r_l * 3 + 2] = lane;
+        if (local_row_out) local_row_out[(size_t)t * K + lane] = r_l;
+    }
+}
+
 }  // namespace mi_ep
 
 using namespace mi_ep;
@@ -1120,6 +1205,43 @@ extern "C" int mi_ep_dispatch_pull_local(const void *my_rows, const void *topk_i
     if (idx_is_i32) { MI_EP_PULL_LOCAL(true); } else { MI_EP_PULL_LOCAL(false); }
 #undef MI_EP_PULL_LOCAL
 #undef MI_EP_PULL_LOCAL2
+    return launch_status();
+}
+
+extern "C" int mi_ep_dispatch_stage_local(const void *x, const void *topk_idx, int idx_is_i32, const int32_t *send_token_idx_small,
+                                          const int32_t *recv_count, const int32_t *num_tokens_per_expert, int T, int K, int H, int E,
+                                          int quant_mode, int rows_hint, void *recv_x, float *recv_x_scales, int32_t *recv_src_idx,
+                                          int32_t *local_row_out, void *stream)
+{
+    if (T < 0 || K <= 0 || K > MI_EP_MAX_TOPK || H <= 0 || H % 16 || H > MI_EP_MAX_HIDDEN || E <= 0)
+        return MI_EP_EINVAL;
+    if (quant_mode != MI_EP_QUANT_NONE && quant_mode != MI_EP_QUANT_INT8 && quant_mode != MI_EP_QUANT_INT8_NOEPS &&
+        quant_mode != MI_EP_QUANT_FP8_E4M3)
+        return MI_EP_EINVAL;
+    if (T == 0 || rows_hint <= 0) return MI_EP_OK;
+    if (!x || !topk_idx || !send_token_idx_small || !recv_count || !num_tokens_per_expert || !recv_x || !recv_src_idx)
+        return MI_EP_EINVAL;
+    const int payload = H * (quant_mode == MI_EP_QUANT_NONE ? 2 : 1);
+    const int blocks = (T + kStageWaves - 1) / kStageWaves;
+    const int nt_from = pull_nt_from_row(rows_hint, payload);
+    const bool nt = nt_from != 0x7fffffff;
+#define MI_EP_STAGE_LOCAL3(I32, QM, NT)                                                                                             \
+    stage_local_kernel<I32, QM, NT><<<blocks, kWave * kStageWaves, 0, (hipStream_t)stream>>>(                                          \
+        (const uint16_t *)x, topk_idx, send_token_idx_small, recv_count, num_tokens_per_expert, T, K, H, E, (uint8_t *)recv_x,       \
+        recv_x_scales, recv_src_idx, rows_hint, nt_from, local_row_out)
+#define MI_EP_STAGE_LOCAL2(I32, QM)                                                                                                 \
+    if (nt) MI_EP_STAGE_LOCAL3(I32, QM, true); else MI_EP_STAGE_LOCAL3(I32, QM, false)
+#define MI_EP_STAGE_LOCAL(QM)                                                                                                       \
+    if (idx_is_i32) { MI_EP_STAGE_LOCAL2(true, QM); } else { MI_EP_STAGE_LOCAL2(false, QM); }
+    switch (quant_mode) {
+        case MI_EP_QUANT_NONE: MI_EP_STAGE_LOCAL(MI_EP_QUANT_NONE); break;
+        case MI_EP_QUANT_INT8: MI_EP_STAGE_LOCAL(MI_EP_QUANT_INT8); break;
+        case MI_EP_QUANT_INT8_NOEPS: MI_EP_STAGE_LOCAL(MI_EP_QUANT_INT8_NOEPS); break;
+        default: MI_EP_STAGE_LOCAL(MI_EP_QUANT_FP8_E4M3); break;
+    }
+#undef MI_EP_STAGE_LOCAL
+#undef MI_EP_STAGE_LOCAL2
+#undef MI_EP_STAGE_LOCAL3
     return launch_status();
 }
 
