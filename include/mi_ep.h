@@ -76,11 +76,23 @@ extern "C" {
 #define MI_EP_QUANT_FP8_E4M3 3  /* per-token OCP FP8 E4M3 (quant_mode "pertoken_fp8_e4m3"): s = amax > 0 ? 448/amax : 1, q = e4m3fn(x * s)
                                  * round-to-nearest-even, scale_out = 1/s (moe_distribute_dispatch_v2_a5.h:1109-1157, the reference's
                                  * Ascend950-only mode; gfx950 converts natively: v_cvt_pk_fp8_f32).  Row layout as INT8: H bytes + meta */
+/* OCP MX block-scaled modes (quant_mode "mx_fp8_e4m3" / "mx_fp8_e5m2" / "mx_fp4_e2m1"; the reference's Ascend950-only modes,
+ * quantize_functions.h ComputeMaxExp / ComputeScale / ComputeFp8Data / ComputeFp4Data).  H % 32 == 0 (else MI_EP_EINVAL).  A row is
+ * cut into H/32 blocks of 32 consecutive elements; e = max over the block of the bf16 exponent field.  Scale byte (E8M0):
+ * 0xFF when e == 0xFF (Inf / NaN in the block; its elements are unspecified), 0 when e == 0 (every element +-0), otherwise
+ * s = max(e - emax, 0) and element = x * 2^(127 - s) rounded to nearest even in the format, saturated to +-max (sign of x kept).
+ * emax / max: E4M3 8 / 448, E5M2 15 / 57344, E2M1 2 / 6.  Staged row: data | scales | meta, data = H bytes (FP8) or H/2 bytes
+ * (FP4: element 2i in the low nibble), scales = H/32 bytes, the meta words at the next 16-byte boundary with the f32 scale word 0.
+ * Receive side: recv_x row r = the data bytes, recv_x_scales (passed as float *, it points to BYTES) + r * H/32 = the scales. */
+#define MI_EP_QUANT_MXFP8_E4M3 4
+#define MI_EP_QUANT_MXFP8_E5M2 5
+#define MI_EP_QUANT_MXFP4_E2M1 6
 
 /* library / build identification ("gfx950") */
 const char *mi_ep_version(void);
 
-/* distance between staged dispatch rows: MI_EP_ROW_STRIDE(hidden * (1 or 2)); the meta words sit right behind the payload */
+/* distance between staged dispatch rows: MI_EP_ROW_STRIDE(payload), payload = hidden * 2 (bf16), hidden (INT8 / per-token FP8),
+ * hidden + hidden/32 (MXFP8), hidden/2 + hidden/32 (MXFP4); the meta words sit behind the payload, at the next multiple of 16 */
 size_t mi_ep_dispatch_row_bytes(int hidden, int quant_mode);
 /* bytes of one combine slot row: hidden * 2 rounded up to 16 */
 size_t mi_ep_combine_row_bytes(int hidden);
@@ -219,7 +231,8 @@ int mi_ep_notify_tables(const int32_t *cnt_matrix, int num_ranks, int num_expert
  * pull: for every output row r < total (= recv_count[L*W-1], read on device): find segment i,
  *   copy row pull_offset[i] + j of src_base[src] into recv_x[r] / recv_x_scales[r] / recv_src_idx[3r..].
  *   `rows_hint` sizes the grid and bounds the rows written (the capacity of the output buffers; normally >= total).
- *   recv_x_scales may be NULL for bf16. */
+ *   recv_x_scales may be NULL for bf16; in the MX modes it points to rows * hidden/32 bytes (E8M0, row r at r * hidden/32) and recv_x
+ *   rows are hidden (MXFP8) or hidden/2 (MXFP4) bytes.  The same holds for every dispatch receive entry point below. */
 int mi_ep_dispatch_stage(const void *x, const void *topk_idx, int idx_is_i32, const int32_t *send_token_idx_small,
                          const int32_t *send_data_offset, int num_tokens, int num_topk, int hidden,
                          int num_experts, int my_rank, int quant_mode, void *rows, void *stream);
@@ -248,7 +261,8 @@ int mi_ep_dispatch_pull_indexed(const void *const *src_base_host, const int32_t 
  * *a_base_out (the lowest source base; the ping-pong half is inside the offset), its scale and its (src, t, k) triple -- what
  * mi_ep_moe_gemm1_swiglu_rows multiplies in place.  All sources must be local memory (push transport, or num_ranks == 1); MI_EP_ESIZE when
  * a staged row could lie 4 GiB or more above the lowest base (the caller then gathers with pull_local / pull_indexed as before).
- * Reference: the MIX kernel multiplies rows where the dispatch left them, csrc/deepep/ops/op_kernel/fused_deep_moe.h:336-427. */
+ * Reference: the MIX kernel multiplies rows where the dispatch left them, csrc/deepep/ops/op_kernel/fused_deep_moe.h:336-427.
+ * The MX modes are not served here (MI_EP_EINVAL). */
 int mi_ep_dispatch_resolve_rows(const void *const *src_base_host, const int32_t *recv_count, const int32_t *pull_offset, int num_ranks,
                                 int num_local_experts, int hidden, int num_topk, int quant_mode, int rows_cap, size_t region_bytes,
                                 const void **a_base_out, uint32_t *row_offsets, float *recv_x_scales, int32_t *recv_src_idx,
@@ -372,7 +386,8 @@ int mi_ep_shared_expert_map(const void *topk_idx, int idx_is_i32, const float *t
  * post_counts: after `send` (stream order) publish count[le][my_rank] granules to every destination.
  * recv: sweep my L*W granules (bounded spin) -> layout_range [L*W] inclusive cumsum, packed_recv_count [L]
  *   int64 (count, or cumulative when count_type == 0), then compact window rows into packed_recv_x /
- *   packed_recv_x_scales / src_info triples in idx-i order. */
+ *   packed_recv_x_scales / src_info triples in idx-i order.
+ * The low-latency entry points take quant modes 0-3 only: the MX modes are MI_EP_EINVAL. */
 int mi_ep_ll_dispatch_send(const void *x, const void *topk_idx, int idx_is_i32, const int32_t *send_token_idx_small,
                            int num_tokens, int num_topk, int hidden, int num_experts, int num_ranks, int my_rank,
                            int max_tokens, int quant_mode, void *const *peer_rows_host, const uint64_t *epoch_ctr,

@@ -55,15 +55,46 @@ int quant_mode_of(bool use_quant, const std::string &quant_type)
 {
     if (!use_quant) return MI_EP_QUANT_NONE;
     if (quant_type == "int8_ll") return MI_EP_QUANT_INT8_NOEPS;     // low-latency rounding (no epsilon), a2a strategy only
-    // per-token FP8 E4M3 is Ascend950-only in the reference (deep_ep.cpp:338-343); gfx950 converts to OCP FP8 natively, so it is
-    // served here.  The block-scaled MXFP8 / MXFP4 modes are not built.
+    // per-token FP8 E4M3 and the block-scaled MXFP8 / MXFP4 modes are Ascend950-only in the reference (deep_ep.cpp:329-365); gfx950
+    // converts to OCP FP8 / FP4 natively, so they are served here (normal dispatch; low-latency dispatch takes int8 / pertoken_fp8_e4m3)
     if (quant_type == "pertoken_fp8_e4m3") return MI_EP_QUANT_FP8_E4M3;
-    EP_HOST_ASSERT_S(quant_type == "int8", quant_type, " is not supported on this device, please use int8, pertoken_fp8_e4m3 or bf16 instead.");
+    if (quant_type == "mx_fp8_e4m3") return MI_EP_QUANT_MXFP8_E4M3;
+    if (quant_type == "mx_fp8_e5m2") return MI_EP_QUANT_MXFP8_E5M2;
+    if (quant_type == "mx_fp4_e2m1") return MI_EP_QUANT_MXFP4_E2M1;
+    EP_HOST_ASSERT_S(quant_type == "int8", quant_type,
+                     " is not supported on this device, please use int8, pertoken_fp8_e4m3, mx_fp8_e4m3, mx_fp8_e5m2, mx_fp4_e2m1 or bf16 instead.");
     return MI_EP_QUANT_INT8;
 }
 
-// dtype of a one-byte-per-element payload tensor (reference deep_ep.cpp:344-365)
-at::ScalarType payload_dtype(int qm) { return qm == MI_EP_QUANT_FP8_E4M3 ? at::kFloat8_e4m3fn : at::kChar; }
+bool quant_is_mx(int qm) { return qm == MI_EP_QUANT_MXFP8_E4M3 || qm == MI_EP_QUANT_MXFP8_E5M2 || qm == MI_EP_QUANT_MXFP4_E2M1; }
+
+// dtype of a quantised payload tensor (reference deep_ep.cpp:344-365)
+at::ScalarType payload_dtype(int qm)
+{
+    switch (qm) {
+        case MI_EP_QUANT_FP8_E4M3:
+        case MI_EP_QUANT_MXFP8_E4M3: return at::kFloat8_e4m3fn;
+        case MI_EP_QUANT_MXFP8_E5M2: return at::kFloat8_e5m2;
+        case MI_EP_QUANT_MXFP4_E2M1: return at::kFloat4_e2m1fn_x2;
+        default: return at::kChar;
+    }
+}
+
+// receive tensors of a quantised dispatch of `rows` rows (reference deep_ep.cpp:344-355): recv_x [rows, H] (MXFP4: [rows, H/2], two
+// elements per byte) and the scales, f32 [rows] per token or E8M0 [rows * H/32] per block of 32 (MX modes)
+at::Tensor recv_payload(int qm, int64_t rows, int H, const at::Device &dev)
+{
+    return at::empty({rows, qm == MI_EP_QUANT_MXFP4_E2M1 ? H / 2 : H}, at::dtype(payload_dtype(qm)).device(dev));
+}
+at::Tensor recv_scales(int qm, int64_t rows, int H, const at::Device &dev)
+{
+    if (quant_is_mx(qm)) return at::empty({rows * (H / 32)}, at::dtype(at::kFloat8_e8m0fnu).device(dev));
+    return at::empty({rows}, at::dtype(at::kFloat).device(dev));
+}
+void check_mx_hidden(int qm, const std::string &quant_type, int H)
+{
+    EP_HOST_ASSERT_S(!quant_is_mx(qm) || H % 32 == 0, "quant_mode ", quant_type, " needs hidden % 32 == 0 (blocks of 32 elements), got hidden = ", H);
+}
 }  // namespace
 
 EventHandle::EventHandle()
@@ -545,8 +576,8 @@ void Buffer::dispatch_pull(const DispatchExchange &ex, int H, int K, int L, int 
 {
     auto dev = x_opts.device();
     const bool quant = qm != MI_EP_QUANT_NONE;
-    rx = quant ? at::empty({rows_alloc, H}, at::dtype(payload_dtype(qm)).device(dev)) : at::empty({rows_alloc, H}, x_opts);
-    rs = at::empty({rows_alloc}, at::dtype(at::kFloat).device(dev));
+    rx = quant ? recv_payload(qm, rows_alloc, H, dev) : at::empty({rows_alloc, H}, x_opts);
+    rs = recv_scales(qm, rows_alloc, H, dev);
     src_idx = at::empty({rows_alloc * 3}, at::dtype(at::kInt).device(dev));
     ProfScope ps_(this, ex.stage_local ? "dispatch_stage_local" : "dispatch_pull", st);
     // this rank's own tokens are gathered token by token (their staged row is read once, not once per selection); everybody else's
@@ -562,20 +593,20 @@ void Buffer::dispatch_pull(const DispatchExchange &ex, int H, int K, int L, int 
         MI_EP_CHECK(mi_ep_dispatch_stage_local(ex.x.data_ptr(), ex.topk_idx.data_ptr(), ex.topk_idx.scalar_type() == at::kInt,
                                                ex.send_token_idx_small.data_ptr<int>(), ex.nt.recv_count.data_ptr<int>(),
                                                ex.num_tokens_per_expert.data_ptr<int>(), ex.num_tokens, K, H, ex.num_experts, qm,
-                                               (int)rows_alloc, rx.data_ptr(), quant ? rs.data_ptr<float>() : nullptr, src_idx.data_ptr<int>(),
+                                               (int)rows_alloc, rx.data_ptr(), quant ? (float *)rs.data_ptr() : nullptr, src_idx.data_ptr<int>(),
                                                local_row_out.defined() ? local_row_out.data_ptr<int>() : nullptr, st));
     else if (local && ex.num_tokens > 0)
         MI_EP_CHECK(mi_ep_dispatch_pull_local(ex.src_bases[(size_t)rank], ex.topk_idx.data_ptr(), ex.topk_idx.scalar_type() == at::kInt,
                                               ex.send_token_idx_small.data_ptr<int>(), ex.nt.recv_count.data_ptr<int>(),
                                               ex.num_tokens_per_expert.data_ptr<int>(), ex.num_tokens, K, H, ex.num_experts, (int)num_ranks,
-                                              (int)rank, qm, (int)rows_alloc, rx.data_ptr(), quant ? rs.data_ptr<float>() : nullptr,
+                                              (int)rank, qm, (int)rows_alloc, rx.data_ptr(), quant ? (float *)rs.data_ptr() : nullptr,
                                               src_idx.data_ptr<int>(), local_row_out.defined() ? local_row_out.data_ptr<int>() : nullptr,
                                               epoch_ctr(kDispatch), region_bytes, st));
     if (local_row_out.defined()) remember_local_rows(src_idx, local_row_out, ex.num_tokens, K);
     if (!(local && num_ranks == 1))
         MI_EP_CHECK(mi_ep_dispatch_pull_indexed((const void *const *)ex.src_bases.data(), ex.nt.recv_count.data_ptr<int>(),
                                                 ex.nt.pull_offset.data_ptr<int>(), (int)num_ranks, L, H, K, qm, (int)rows_alloc,
-                                                ex.slab_bytes, rx.data_ptr(), quant ? rs.data_ptr<float>() : nullptr,
+                                                ex.slab_bytes, rx.data_ptr(), quant ? (float *)rs.data_ptr() : nullptr,
                                                 src_idx.data_ptr<int>(), epoch_ctr(kDispatch), region_bytes, local ? (int)rank : -1, st));
 }
 
@@ -619,6 +650,7 @@ Buffer::intranode_dispatch(const at::Tensor &x, const std::optional<at::Tensor> 
     EP_HOST_ASSERT_S(H % 16 == 0 && H <= MI_EP_MAX_HIDDEN, "hidden (", H, ") must be a multiple of 16 and <= ", MI_EP_MAX_HIDDEN);
     EP_HOST_ASSERT_S(E <= 2048, "num_experts (", E, ") must be <= 2048");
     const int qm = quant_mode_of(use_quant, quant_type);
+    check_mx_hidden(qm, quant_type, H);
     check_status("intranode_dispatch");
     ++profile_calls;
     const Layout &lay = layout_for(*topk_idx, E);
@@ -692,7 +724,7 @@ Buffer::intranode_dispatch(const at::Tensor &x, const std::optional<at::Tensor> 
     const int64_t rows = trt == 0 ? 1 : trt;      // deep_ep.cpp:327-328
     if (guess >= rows) {
         expandx_out = expandx_out.narrow(0, 0, rows);
-        dynamic_scales_out = dynamic_scales_out.narrow(0, 0, rows);
+        dynamic_scales_out = dynamic_scales_out.narrow(0, 0, quant_is_mx(qm) ? rows * (H / 32) : rows);
         expand_idx_out = expand_idx_out.narrow(0, 0, rows * 3);
     } else {
         dispatch_pull(ex, H, K, L, qm, rows, x.options(), expandx_out, dynamic_scales_out, expand_idx_out, st);
@@ -1504,6 +1536,7 @@ std::tuple<at::Tensor, at::Tensor> Buffer::a2a_dispatch_stage(const at::Tensor &
     EP_HOST_ASSERT(x.dim() == 2 and x.is_contiguous() and x.scalar_type() == at::kBFloat16);
     const int T = (int)x.size(0), H = (int)x.size(1), K = (int)topk_idx.size(1), E = (int)num_experts;
     const int qm = quant_mode_of(quant_type != "bf16", quant_type);
+    check_mx_hidden(qm, quant_type, H);
     const Layout &lay = layout_for(topk_idx, E);
     const size_t rb = mi_ep_dispatch_row_bytes(H, qm);
     auto rows = at::empty({std::max<int64_t>((int64_t)T * K, 1), (int64_t)rb}, at::dtype(at::kByte).device(x.device()));
@@ -1568,12 +1601,11 @@ Buffer::a2a_dispatch_unpack(const at::Tensor &staging, const std::vector<int64_t
     EP_HOST_ASSERT(off == total_recv);
     const int64_t rows = std::max<int64_t>(total_recv == 0 ? 1 : total_recv, min_rows);
     auto dev = staging.device();
-    at::Tensor recv_x = use_quant ? at::empty({rows, H}, at::dtype(payload_dtype(qm)).device(dev))
-                                  : at::empty({rows, H}, at::dtype(at::kBFloat16).device(dev));
-    at::Tensor scales = at::empty({rows}, at::dtype(at::kFloat).device(dev));
+    at::Tensor recv_x = use_quant ? recv_payload(qm, rows, H, dev) : at::empty({rows, H}, at::dtype(at::kBFloat16).device(dev));
+    at::Tensor scales = recv_scales(qm, rows, H, dev);
     at::Tensor src_idx = at::empty({std::max<int64_t>(rows * 3, src_idx_len)}, at::dtype(at::kInt).device(dev));
     MI_EP_CHECK(mi_ep_dispatch_pull(bases.data(), recv_count.data_ptr<int>(), pull_offset.data_ptr<int>(), W, L, H, qm,
-                                    (int)total_recv, recv_x.data_ptr(), use_quant ? scales.data_ptr<float>() : nullptr,
+                                    (int)total_recv, recv_x.data_ptr(), use_quant ? (float *)scales.data_ptr() : nullptr,
                                     src_idx.data_ptr<int>(), cur_stream()));
     return {recv_x, use_quant ? std::optional<at::Tensor>(scales) : std::nullopt, src_idx};
 }

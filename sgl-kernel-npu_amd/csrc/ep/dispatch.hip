@@ -219,6 +219,107 @@ __device__ __forceinline__ void quant_row(u32x4 (&raw)[kMaxItems][2], u32x4 (&q)
             }
     }
 }
+// QM = MI_EP_QUANT_MXFP8_E4M3 / _E5M2 / MXFP4_E2M1 (include/mi_ep.h): OCP MX blocks of 32 elements.  Item it * kWave + lane holds 16
+// consecutive elements, so block it * 32 + m is the lane pair (2m, 2m + 1): the block's exponent maximum is the pair's, one DPP step,
+// no wave-wide reduction.  q[it] = the item's 16 FP8 bytes (MXFP4: 8 bytes in q[it].xy, element 2i in the low nibble); sc[it] = the
+// block's E8M0 scale byte, in both lanes of the pair.
+template <int QM>
+__device__ __forceinline__ void quant_row_mx(const u32x4 (&raw)[kMaxItems][2], u32x4 (&q)[kMaxItems], uint32_t (&sc)[kMaxItems])
+{
+    constexpr uint32_t kEmax = QM == MI_EP_QUANT_MXFP8_E4M3 ? 8u : QM == MI_EP_QUANT_MXFP8_E5M2 ? 15u : 2u;
+    constexpr float kMaxF = QM == MI_EP_QUANT_MXFP8_E4M3 ? 448.0f : QM == MI_EP_QUANT_MXFP8_E5M2 ? 57344.0f : 6.0f;
+    typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int it = 0; it < kMaxItems; ++it) {
+        // exponent fields, two elements per v_pk_max_u16 (items past H / 16 are zero: e = 0, never stored)
+        u16x2 m2 = u16x2{0, 0};
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(u16x2, raw[it][h][j] & 0x7F807F80u));
+        uint32_t e = (uint32_t)(m2[0] > m2[1] ? m2[0] : m2[1]) >> 7;
+        e = max(e, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)e, 0xB1, 0xF, 0xF, false));      // quad_perm [1,0,3,2]: the lane pair
+        const uint32_t s = e > kEmax ? e - kEmax : 0u;
+        sc[it] = e == 0xFFu ? 0xFFu : s;                      // Inf / NaN in the block: 0xFF, its elements unspecified
+        // 2^(127 - s) as bits; a block of zeros and bf16 subnormals (e == 0) multiplies by 0: every element +-0
+        const float mul = e == 0u ? 0.0f : __uint_as_float((254u - s) << 23);
+        uint32_t out[4];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+                const uint32_t w0 = raw[it][h][jj * 2], w1 = raw[it][h][jj * 2 + 1];
+                // exact power-of-two product, clamped to +-max before the conversion so that the result does not depend on how the
+                // conversion instruction treats out-of-range input; the conversions round to nearest even
+                const float a0 = __builtin_amdgcn_fmed3f(bf16_to_f32(w0 & 0xFFFFu) * mul, -kMaxF, kMaxF);
+                const float a1 = __builtin_amdgcn_fmed3f(__uint_as_float(w0 & 0xFFFF0000u) * mul, -kMaxF, kMaxF);
+                const float b0 = __builtin_amdgcn_fmed3f(bf16_to_f32(w1 & 0xFFFFu) * mul, -kMaxF, kMaxF);
+                const float b1 = __builtin_amdgcn_fmed3f(__uint_as_float(w1 & 0xFFFF0000u) * mul, -kMaxF, kMaxF);
+                uint32_t p;
+                if constexpr (QM == MI_EP_QUANT_MXFP8_E4M3) {
+                    p = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a0, a1, 0, false);
+                    p = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(b0, b1, (int)p, true);
+                } else if constexpr (QM == MI_EP_QUANT_MXFP8_E5M2) {
+                    p = (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(a0, a1, 0, false);
+                    p = (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(b0, b1, (int)p, true);
+                } else {                                       // two bytes of the item's FP4 dword h (scale operand 1.0)
+                    p = jj ? out[h] : 0u;
+                    if (jj == 0) {
+                        p = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(p, a0, a1, 1.0f, 0);
+                        p = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(p, b0, b1, 1.0f, 1);
+                    } else {
+                        p = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(p, a0, a1, 1.0f, 2);
+                        p = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(p, b0, b1, 1.0f, 3);
+                    }
+                }
+                if constexpr (QM == MI_EP_QUANT_MXFP4_E2M1) out[h] = p;
+                else out[h * 2 + jj] = p;
+            }
+        if constexpr (QM == MI_EP_QUANT_MXFP4_E2M1) q[it] = u32x4{out[0], out[1], 0u, 0u};
+        else q[it] = u32x4{out[0], out[1], out[2], out[3]};
+    }
+}
+// Block scales of item group `it` (blocks it * 32 .. it * 32 + 31) to sc_row[block], blocks < nsc only.  dw (wave-uniform): sc_row is
+// 4-byte aligned and may be written up to the next multiple of 4 past nsc (staged rows: the pad in front of the meta words, receive
+// rows when nsc % 4 == 0) -- the pair's bytes are gathered into dwords (one DPP step, one shuffle) and lane 8d stores blocks 4d..4d+3;
+// otherwise one byte per lane pair.  Called by the whole wave.
+__device__ __forceinline__ void st_block_scales(uint8_t *sc_row, int it, uint32_t s, int nsc, bool dw, int lane)
+{
+    const int b = it * 32 + (lane >> 1);
+    if (dw) {
+        uint32_t t = s | ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x4E, 0xF, 0xF, false) << 8);     // quad_perm [2,3,0,1]
+        t |= (uint32_t)__shfl_down((int)t, 4, kWave) << 16;
+        if ((lane & 7) == 0 && b < nsc) *(uint32_t *)(sc_row + b) = t;
+    } else if ((lane & 1) == 0 && b < nsc) {
+        sc_row[b] = (uint8_t)s;
+    }
+}
+// One quantised row: items (16 B per lane; MXFP4 8 B) to `row`, MX block scales to sc_row (see st_block_scales).  Called by the whole wave.
+template <int QM, bool NT>
+__device__ __forceinline__ void st_quant_row(uint8_t *row, uint8_t *sc_row, bool sc_dw, int H, const u32x4 (&q)[kMaxItems],
+                                             const uint32_t (&sc)[kMaxItems], int lane)
+{
+    const int nitems = H / 16;
+#pragma unroll
+    for (int it = 0; it < kMaxItems; ++it) {
+        const int item = it * kWave + lane;
+        if (item < nitems) {
+            if constexpr (QM == MI_EP_QUANT_MXFP4_E2M1) {
+                const u32x2 v = u32x2{q[it][0], q[it][1]};
+                if (NT) __builtin_nontemporal_store(v, (u32x2 *)row + item);
+                else ((u32x2 *)row)[item] = v;
+            } else {
+                if (NT) __builtin_nontemporal_store(q[it], (u32x4 *)row + item);
+                else ((u32x4 *)row)[item] = q[it];
+            }
+        }
+    }
+    if constexpr (quant_is_mx(QM)) {
+#pragma unroll
+        for (int it = 0; it < kMaxItems; ++it)
+            if (it * kWave < nitems) st_block_scales(sc_row, it, sc[it], H / 32, sc_dw, lane);     // wave-uniform condition
+    }
+}
 template <bool I32, int QM, bool LATE>
 __device__ __forceinline__ void stage_int8_body(
     const uint16_t *__restrict__ x, const void *__restrict__ topk_idx, const int32_t *__restrict__ idx_small,
@@ -230,7 +331,9 @@ __device__ __forceinline__ void stage_int8_body(
     const int t = wid / ksplit, kpart = wid - t * ksplit;
     if (t >= T) return;
     const int nitems = H / 16;
-    const size_t stride = MI_EP_ROW_STRIDE(H);
+    constexpr bool kMx = quant_is_mx(QM);
+    const RowPayload pl = row_payload(H, QM);
+    const size_t stride = pl.stride();
     // the row is requested before the routing is known (a token that selects nothing is the rare case): behind the routing's two
     // dependent loads (expert id, then slot and segment offset) the 14 KB of the row started one to two round trips late
     u32x4 raw[kMaxItems][2];
@@ -245,9 +348,11 @@ __device__ __forceinline__ void stage_int8_body(
     if (!LATE) route_token<I32, false>(ll, topk_idx, idx_small, send_off, t, K, E, my_rank, late, e_l, slot_l, dst_l);
     const unsigned long long vmask = __ballot(e_l >= 0);
     if (vmask == 0ull) return;      // token selects nothing: no row is produced
-    float scale_out;
+    float scale_out = 0.f;                              // MX modes: the meta's scale word is 0
     u32x4 q[kMaxItems];
-    quant_row<QM>(raw, q, scale_out);
+    uint32_t sc[kMaxItems];
+    if constexpr (kMx) quant_row_mx<QM>(raw, q, sc);
+    else quant_row<QM>(raw, q, scale_out);
     if (LATE) route_token<I32, true>(ll, topk_idx, idx_small, send_off, t, K, E, my_rank, late, e_l, slot_l, dst_l);
     if (idx_off) {
         // compact staging (normal-mode pull transport): the row is written ONCE at slot t; the expert-sorted index tells the
@@ -255,13 +360,17 @@ __device__ __forceinline__ void stage_int8_body(
         // Push transport: the same row + index entries, written into every destination rank's window instead of the own one.
         stage_token_rows(pg, dsts, parity_off(par), idx_off, my_rank, t, K, e_l, slot_l, send_off, [&](uint8_t *base) {
             uint8_t *row = base + (size_t)t * stride;
-            u32x4 *dst = (u32x4 *)row;
+            if constexpr (kMx) {
+                st_quant_row<QM, false>(row, row + pl.data, true, H, q, sc, lane);
+            } else {
+                u32x4 *dst = (u32x4 *)row;
 #pragma unroll
-            for (int it = 0; it < kMaxItems; ++it) {
-                const int item = it * kWave + lane;
-                if (item < nitems) dst[item] = q[it];
+                for (int it = 0; it < kMaxItems; ++it) {
+                    const int item = it * kWave + lane;
+                    if (item < nitems) dst[item] = q[it];
+                }
             }
-            if (lane == 0) *(u32x4 *)(row + H) = u32x4{__float_as_uint(scale_out), (uint32_t)t, 0u, (uint32_t)my_rank};
+            if (lane == 0) *(u32x4 *)(row + pl.meta_off()) = u32x4{__float_as_uint(scale_out), (uint32_t)t, 0u, (uint32_t)my_rank};
         });
         return;
     }
@@ -289,13 +398,17 @@ __device__ __forceinline__ void stage_int8_body(
             if (lane == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wt_u32x4, m), d, H, 0, 17);
             continue;
         }
-        u32x4 *dst = (u32x4 *)row;
+        if constexpr (kMx) {
+            st_quant_row<QM, false>(row, row + pl.data, true, H, q, sc, lane);
+        } else {
+            u32x4 *dst = (u32x4 *)row;
 #pragma unroll
-        for (int it = 0; it < kMaxItems; ++it) {
-            const int item = it * kWave + lane;
-            if (item < nitems) dst[item] = q[it];
+            for (int it = 0; it < kMaxItems; ++it) {
+                const int item = it * kWave + lane;
+                if (item < nitems) dst[item] = q[it];
+            }
         }
-        if (lane == 0) *(u32x4 *)(row + H) = meta;
+        if (lane == 0) *(u32x4 *)(row + pl.meta_off()) = meta;
     }
 }
 
@@ -563,17 +676,52 @@ __global__ __launch_bounds__(1024) void ll_layout_send_kernel(
 constexpr int kPullWaves = 4;
 constexpr int kPullRowsPerBlock = kPullWaves;              // grid sizing: one row per wave until the chip is full (2048 workgroups)
 
+// MX block scales of one row (n <= MI_EP_MAX_HIDDEN / 32 bytes) held by the wave: one dword per lane when n % 4 == 0 (the receive rows
+// are then dword-aligned), else up to four bytes per lane (byte i at lane i % 64, slot i / 64)
+__device__ __forceinline__ void ld_block_scales(const uint8_t *s, int n, int lane, uint32_t (&v)[4])
+{
+    if ((n & 3) == 0) {
+        v[0] = lane < n / 4 ? ((const uint32_t *)s)[lane] : 0u;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = lane + j * kWave < n ? s[lane + j * kWave] : 0u;
+}
+__device__ __forceinline__ void st_block_scales_row(uint8_t *d, int n, int lane, const uint32_t (&v)[4])
+{
+    if ((n & 3) == 0) {
+        if (lane < n / 4) ((uint32_t *)d)[lane] = v[0];
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (lane + j * kWave < n) d[lane + j * kWave] = (uint8_t)v[j];
+}
+// the scales of receive row r from staged row `srow`: MX block scales to (bytes) recv_scales + r * pl.scales by the whole wave, else
+// (quantised modes) the f32 word of the meta by lane 0
+__device__ __forceinline__ void recv_row_scales(const uint8_t *srow, const RowPayload &pl, float *recv_scales, long long r, int lane)
+{
+    if (!recv_scales) return;
+    if (pl.scales) {
+        uint32_t v[4];
+        ld_block_scales(srow + pl.data, pl.scales, lane, v);
+        st_block_scales_row((uint8_t *)recv_scales + (size_t)r * pl.scales, pl.scales, lane, v);
+    } else if (lane == 0) {
+        recv_scales[r] = *(const float *)(srow + pl.meta_off());
+    }
+}
+
 // rows [0, total) of the receive buffers from the (local expert, source) segments described by the inclusive cumsum in LDS
 __device__ __forceinline__ void pull_body(
     const PeerPtrs &srcs, const int32_t *cum /*LDS [LW]*/, const int32_t *__restrict__ pull_offset, int seg_capacity, int W, int LW,
-    int payload_bytes /*H or 2H*/, uint8_t *__restrict__ recv_x, float *__restrict__ recv_scales, int32_t *__restrict__ recv_src_idx,
+    RowPayload pl, uint8_t *__restrict__ recv_x, float *__restrict__ recv_scales, int32_t *__restrict__ recv_src_idx,
     int row_capacity, size_t poff)
 {
     const int total = min(cum[LW - 1], row_capacity);      // never write past the caller's buffers
     const int lane = lane_id();
     const int wave = threadIdx.x / kWave;
-    const size_t stride = MI_EP_ROW_STRIDE(payload_bytes);
-    const int n16 = payload_bytes / 16;
+    const size_t stride = pl.stride();
+    const int n16 = pl.data / 16;
     // rows are dealt to waves round-robin over the whole grid: a decode-size exchange (1 K rows) still spreads over every CU,
     // a prefill-size one gives each wave a few rows a grid-width apart
     {
@@ -591,11 +739,11 @@ __device__ __forceinline__ void pull_body(
             const size_t off = pull_offset ? (size_t)pull_offset[i] : (size_t)i * seg_capacity;
             const uint8_t *srow = (const uint8_t *)srcs.p[src] + poff + (off + j) * stride;
             const u32x4 *s16 = (const u32x4 *)srow;
-            u32x4 *d16 = (u32x4 *)(recv_x + (size_t)r * payload_bytes);
+            u32x4 *d16 = (u32x4 *)(recv_x + (size_t)r * pl.data);
             copy_row<true, false>(s16, d16, n16, lane);           // straight-line groups of 1 KB pieces (ep_common.h)
+            recv_row_scales(srow, pl, recv_scales, r, lane);
             if (lane == 0) {
-                const u32x4 m = *(const u32x4 *)(srow + payload_bytes);
-                if (recv_scales) recv_scales[r] = __uint_as_float(m[0]);
+                const u32x4 m = *(const u32x4 *)(srow + pl.meta_off());
                 recv_src_idx[r * 3 + 0] = (int32_t)m[3];
                 recv_src_idx[r * 3 + 1] = (int32_t)m[1];
                 recv_src_idx[r * 3 + 2] = (int32_t)m[2];
@@ -634,13 +782,13 @@ static int pull_nt_from_row(long long rows, int payload)
 
 __global__ __launch_bounds__(kWave * kPullWaves) void pull_kernel(
     PeerPtrs srcs, const int32_t *__restrict__ recv_count, const int32_t *__restrict__ pull_offset, int seg_capacity,
-    int W, int LW, int payload_bytes, uint8_t *__restrict__ recv_x, float *__restrict__ recv_scales,
+    int W, int LW, RowPayload pl, uint8_t *__restrict__ recv_x, float *__restrict__ recv_scales,
     int32_t *__restrict__ recv_src_idx, int row_capacity, Parity par)
 {
     extern __shared__ __attribute__((aligned(16))) int32_t cum[];    // [LW] inclusive cumsum
     for (int i = threadIdx.x; i < LW; i += blockDim.x) cum[i] = recv_count[i];
     __syncthreads();
-    pull_body(srcs, cum, pull_offset, seg_capacity, W, LW, payload_bytes, recv_x, recv_scales, recv_src_idx, row_capacity,
+    pull_body(srcs, cum, pull_offset, seg_capacity, W, LW, pl, recv_x, recv_scales, recv_src_idx, row_capacity,
               parity_off(par));
 }
 
@@ -745,7 +893,7 @@ __global__ __launch_bounds__(kWave * kPullWaves) void ll_wait_pack_kernel(
 template <bool NT>
 __global__ __launch_bounds__(kWave * kPullWaves) void pull_indexed_kernel(
     PeerPtrs srcs, const int32_t *__restrict__ recv_count, const int32_t *__restrict__ pull_offset, int W, int LW,
-    int payload_bytes, size_t idx_off, size_t idx_entries, uint8_t *__restrict__ recv_x, float *__restrict__ recv_scales,
+    RowPayload pl, size_t idx_off, size_t idx_entries, uint8_t *__restrict__ recv_x, float *__restrict__ recv_scales,
     int32_t *__restrict__ recv_src_idx, int row_capacity, Parity par, int skip_src, int nt_from_row)
 {
     extern __shared__ __attribute__((aligned(16))) int32_t cum[];    // [LW] inclusive cumsum
@@ -755,8 +903,8 @@ __global__ __launch_bounds__(kWave * kPullWaves) void pull_indexed_kernel(
     const int total = min(cum[LW - 1], row_capacity);
     const int lane = lane_id();
     const int wave = threadIdx.x / kWave;
-    const size_t stride = MI_EP_ROW_STRIDE(payload_bytes);
-    const int n16 = payload_bytes / 16;
+    const size_t stride = pl.stride();
+    const int n16 = pl.data / 16;
     const long long nw = (long long)gridDim.x * kPullWaves;
     auto entry = [&](long long r, int &src) -> uint2 {          // wave-uniform
         int lo = 0, hi = LW - 1;
@@ -789,12 +937,12 @@ __global__ __launch_bounds__(kWave * kPullWaves) void pull_indexed_kernel(
         const size_t trow = min((size_t)e.x, idx_off / stride - 1);
         const uint8_t *srow = (const uint8_t *)srcs.p[src] + poff + trow * stride;
         const u32x4 *s16 = (const u32x4 *)srow;
-        u32x4 *d16 = (u32x4 *)(recv_x + (size_t)r * payload_bytes);
+        u32x4 *d16 = (u32x4 *)(recv_x + (size_t)r * pl.data);
         // straight-line groups of 1 KB pieces (ep_common.h); plain loads: a token row is read up to K times
         if (NT && r >= nt_from_row) copy_row<false, true>(s16, d16, n16, lane);
         else copy_row<false, false>(s16, d16, n16, lane);
+        recv_row_scales(srow, pl, recv_scales, r, lane);
         if (lane == 0) {
-            if (recv_scales) recv_scales[r] = *(const float *)(srow + payload_bytes);
             recv_src_idx[r * 3 + 0] = src;
             recv_src_idx[r * 3 + 1] = (int32_t)e.x;
             recv_src_idx[r * 3 + 2] = (int32_t)e.y;
@@ -854,7 +1002,7 @@ template <bool I32, bool NT>
 __global__ __launch_bounds__(kWave * kPullWaves) void pull_local_kernel(
     const uint8_t *__restrict__ my_rows, const void *__restrict__ topk_idx, const int32_t *__restrict__ idx_small,
     const int32_t *__restrict__ recv_count, const int32_t *__restrict__ tokens_per_expert, int T, int K, int E, int W, int my_rank,
-    int payload_bytes, uint8_t *__restrict__ recv_x, float *__restrict__ recv_scales, int32_t *__restrict__ recv_src_idx,
+    RowPayload pl, uint8_t *__restrict__ recv_x, float *__restrict__ recv_scales, int32_t *__restrict__ recv_src_idx,
     int row_capacity, Parity par, int nt_from_row, int32_t *__restrict__ local_row_out)
 {
     const int lane = lane_id();
@@ -862,17 +1010,19 @@ __global__ __launch_bounds__(kWave * kPullWaves) void pull_local_kernel(
     if (t >= T) return;
     // the first part of the row is requested before the routing is known (a token without a selection on this rank is the rare case at
     // the sizes where this kernel matters): the routing costs three dependent loads
-    const size_t stride = MI_EP_ROW_STRIDE(payload_bytes);
+    const size_t stride = pl.stride();
     const uint8_t *srow = my_rows + parity_off(par) + (size_t)t * stride;
     const u32x4 *s16 = (const u32x4 *)srow;
-    const int n16 = payload_bytes / 16;
+    const int n16 = pl.data / 16;
     u32x4 v[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int item = u * kWave + lane;
         if (item < n16) v[u] = s16[item];
     }
-    const float scale = *(const float *)(srow + payload_bytes);
+    const float scale = *(const float *)(srow + pl.meta_off());
+    uint32_t bsc[4];                                              // MX block scales of the row
+    if (pl.scales) ld_block_scales(srow + pl.data, pl.scales, lane, bsc);
     const uint32_t L = (uint32_t)(E / W);
     int r_l = -1;
     if (lane < K) {
@@ -899,7 +1049,8 @@ __global__ __launch_bounds__(kWave * kPullWaves) void pull_local_kernel(
         for (unsigned long long m = lmask; m; m &= m - 1) {       // wave-uniform walk over this rank's selections of the token
             const int k = __builtin_ctzll(m);
             const int rk = __builtin_amdgcn_readlane(r_l, k);
-            u32x4 *d16 = (u32x4 *)(recv_x + (size_t)rk * payload_bytes);
+            u32x4 *d16 = (u32x4 *)(recv_x + (size_t)rk * pl.data);
+            if (base == 0 && pl.scales && recv_scales) st_block_scales_row((uint8_t *)recv_scales + (size_t)rk * pl.scales, pl.scales, lane, bsc);
             if (NT && rk >= nt_from_row) {
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
@@ -916,7 +1067,7 @@ __global__ __launch_bounds__(kWave * kPullWaves) void pull_local_kernel(
         }
     }
     if (r_l >= 0) {                                               // lane k writes the meta of selection k
-        if (recv_scales) recv_scales[r_l] = scale;
+        if (recv_scales && !pl.scales) recv_scales[r_l] = scale;
         recv_src_idx[(size_t)r_l * 3 + 0] = my_rank;
         recv_src_idx[(size_t)r_l * 3 + 1] = t;
         recv_src_idx[(size_t)r_l * 3 + 2] = lane;
@@ -938,7 +1089,7 @@ __global__ __launch_bounds__(kWave * kStageWaves) void stage_local_kernel(
     uint8_t *__restrict__ recv_x, float *__restrict__ recv_scales, int32_t *__restrict__ recv_src_idx, int row_capacity,
     int nt_from_row, int32_t *__restrict__ local_row_out)
 {
-    constexpr bool kQuant = QM != MI_EP_QUANT_NONE;
+    constexpr bool kQuant = QM != MI_EP_QUANT_NONE, kMx = quant_is_mx(QM);
     constexpr int kIt = kQuant ? kMaxItems : kChunkItems;
     const int lane = lane_id();
     const int t = __builtin_amdgcn_readfirstlane(blockIdx.x * kStageWaves + threadIdx.x / kWave);
@@ -959,13 +1110,21 @@ __global__ __launch_bounds__(kWave * kStageWaves) void stage_local_kernel(
     const unsigned long long lmask = __ballot(r_l >= 0);
     if (lmask == 0ull) return;                                    // token selects nothing: no row is produced
     float scale = 0.f;                                            // bf16 rows: the staged meta's scale word is 0 as well
-    if constexpr (kQuant) quant_row<QM>(raw, q, scale);
+    uint32_t sc[kMaxItems];
+    if constexpr (kMx) quant_row_mx<QM>(raw, q, sc);
+    else if constexpr (kQuant) quant_row<QM>(raw, q, scale);
     const int n16 = kQuant ? H / 16 : H / 8;
-    const size_t payload = kQuant ? (size_t)H : (size_t)H * 2;
+    const RowPayload pl = row_payload(H, QM);
     for (unsigned long long m = lmask; m; m &= m - 1) {           // wave-uniform walk over the token's selections
         const int k = __builtin_ctzll(m);
         const int rk = __builtin_amdgcn_readlane(r_l, k);
-        u32x4 *d16 = (u32x4 *)(recv_x + (size_t)rk * payload);
+        if constexpr (kMx) {
+            uint8_t *row = recv_x + (size_t)rk * pl.data, *sc_row = (uint8_t *)recv_scales + (size_t)rk * pl.scales;
+            if (NT && rk >= nt_from_row) st_quant_row<QM, true>(row, sc_row, (pl.scales & 3) == 0, H, q, sc, lane);
+            else st_quant_row<QM, false>(row, sc_row, (pl.scales & 3) == 0, H, q, sc, lane);
+            continue;
+        }
+        u32x4 *d16 = (u32x4 *)(recv_x + (size_t)rk * pl.data);
         if (NT && rk >= nt_from_row) {
 #pragma unroll
             for (int it = 0; it < kIt; ++it) {
@@ -981,7 +1140,7 @@ __global__ __launch_bounds__(kWave * kStageWaves) void stage_local_kernel(
         }
     }
     if (r_l >= 0) {                                               // lane k writes the meta of selection k
-        if (recv_scales) recv_scales[r_l] = scale;
+        if (recv_scales && !kMx) recv_scales[r_l] = scale;
         recv_src_idx[(size_t)r_l * 3 + 0] = 0;
         recv_src_idx[(size_t)r_l * 3 + 1] = t;
         recv_src_idx[(size_t)r_l * 3 + 2] = lane;
@@ -995,7 +1154,7 @@ using namespace mi_ep;
 
 extern "C" size_t mi_ep_dispatch_row_bytes(int hidden, int quant_mode)
 {
-    return MI_EP_ROW_STRIDE((size_t)hidden * (quant_mode == MI_EP_QUANT_NONE ? 2 : 1));
+    return row_payload(hidden, quant_mode).stride();
 }
 
 extern "C" size_t mi_ep_dispatch_index_offset(int hidden, int quant_mode, int topk, size_t region_bytes)
@@ -1010,7 +1169,7 @@ static int stage_launch(const void *x, const void *topk_idx, int idx_is_i32, con
                         size_t idx_off, void *stream, const PeerPtrs *push_peers = nullptr, PushGeom pg = PushGeom{0, 0},
                         Parity par = Parity{EpochRef{nullptr, 0}, 0})
 {
-    if (T < 0 || K <= 0 || K > MI_EP_MAX_TOPK || H <= 0 || H % 16 || H > MI_EP_MAX_HIDDEN || E <= 0) return MI_EP_EINVAL;
+    if (T < 0 || K <= 0 || K > MI_EP_MAX_TOPK || !dispatch_mode_ok(quant_mode, H) || H > MI_EP_MAX_HIDDEN || E <= 0) return MI_EP_EINVAL;
     if (T == 0) return MI_EP_OK;
     if (!x || !topk_idx || !send_token_idx_small || !send_data_offset || (!rows && !push_peers)) return MI_EP_EINVAL;
     hipStream_t s = (hipStream_t)stream;
@@ -1037,6 +1196,15 @@ static int stage_launch(const void *x, const void *topk_idx, int idx_is_i32, con
             break;
         case MI_EP_QUANT_FP8_E4M3:
             if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_FP8_E4M3>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_FP8_E4M3>));
+            break;
+        case MI_EP_QUANT_MXFP8_E4M3:
+            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_MXFP8_E4M3>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_MXFP8_E4M3>));
+            break;
+        case MI_EP_QUANT_MXFP8_E5M2:
+            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_MXFP8_E5M2>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_MXFP8_E5M2>));
+            break;
+        case MI_EP_QUANT_MXFP4_E2M1:
+            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_MXFP4_E2M1>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_MXFP4_E2M1>));
             break;
         default:
             return MI_EP_EINVAL;
@@ -1096,8 +1264,8 @@ extern "C" int mi_ep_dispatch_pull(const void *const *src_base_host, const int32
                                    const int32_t *pull_offset, int W, int L, int H, int quant_mode, int rows_hint,
                                    void *recv_x, float *recv_x_scales, int32_t *recv_src_idx, void *stream)
 {
-    if (!src_base_host || !recv_count || !pull_offset || W <= 0 || W > MI_EP_MAX_RANKS || L <= 0 || H <= 0 || H % 16 ||
-        !recv_x || !recv_src_idx)
+    if (!src_base_host || !recv_count || !pull_offset || W <= 0 || W > MI_EP_MAX_RANKS || L <= 0 || !dispatch_mode_ok(quant_mode, H) ||
+        !recv_x || !recv_src_idx || (quant_is_mx(quant_mode) && !recv_x_scales))
         return MI_EP_EINVAL;
     if (rows_hint <= 0) return MI_EP_OK;
     PeerPtrs pp;
@@ -1105,12 +1273,12 @@ extern "C" int mi_ep_dispatch_pull(const void *const *src_base_host, const int32
         if (!src_base_host[i]) return MI_EP_EINVAL;
         pp.p[i] = const_cast<void *>(src_base_host[i]);
     }
-    const int payload = H * (quant_mode == MI_EP_QUANT_NONE ? 2 : 1);
+    const RowPayload pl = row_payload(H, quant_mode);
     long long blocks = ((long long)rows_hint + kPullRowsPerBlock - 1) / kPullRowsPerBlock;
     if (blocks > 256 * 8) blocks = 256 * 8;
     const size_t lds = (size_t)L * W * sizeof(int32_t);
     pull_kernel<<<(int)blocks, kWave * kPullWaves, lds, (hipStream_t)stream>>>(
-        pp, recv_count, pull_offset, 0, W, L * W, payload, (uint8_t *)recv_x, recv_x_scales, recv_src_idx, rows_hint,
+        pp, recv_count, pull_offset, 0, W, L * W, pl, (uint8_t *)recv_x, recv_x_scales, recv_src_idx, rows_hint,
         Parity{EpochRef{nullptr, 0}, 0});
     return launch_status();
 }
@@ -1121,8 +1289,8 @@ extern "C" int mi_ep_dispatch_pull_indexed(const void *const *src_base_host, con
                                            int32_t *recv_src_idx, const uint64_t *epoch_ctr, size_t parity_stride, int skip_src,
                                            void *stream)
 {
-    if (!src_base_host || !recv_count || !pull_offset || W <= 0 || W > MI_EP_MAX_RANKS || L <= 0 || H <= 0 || H % 16 || K <= 0 ||
-        K > MI_EP_MAX_TOPK || !recv_x || !recv_src_idx || skip_src >= W)
+    if (!src_base_host || !recv_count || !pull_offset || W <= 0 || W > MI_EP_MAX_RANKS || L <= 0 || !dispatch_mode_ok(quant_mode, H) || K <= 0 ||
+        K > MI_EP_MAX_TOPK || !recv_x || !recv_src_idx || skip_src >= W || (quant_is_mx(quant_mode) && !recv_x_scales))
         return MI_EP_EINVAL;
     if (rows_hint <= 0) return MI_EP_OK;
     PeerPtrs pp;
@@ -1132,17 +1300,17 @@ extern "C" int mi_ep_dispatch_pull_indexed(const void *const *src_base_host, con
     }
     const size_t idx_off = mi_ep_dispatch_index_offset(H, quant_mode, K, region_bytes);
     if (idx_off == 0) return MI_EP_EINVAL;
-    const int payload = H * (quant_mode == MI_EP_QUANT_NONE ? 2 : 1);
+    const RowPayload pl = row_payload(H, quant_mode);
     long long blocks = ((long long)rows_hint + kPullRowsPerBlock - 1) / kPullRowsPerBlock;
     static const long long cap = getenv("MI_EP_PULL_BLOCKS") ? atoll(getenv("MI_EP_PULL_BLOCKS")) : 256 * 8;
     if (blocks > cap) blocks = cap;
     const size_t lds = (size_t)L * W * sizeof(int32_t);
 #define MI_EP_PULL_INDEXED(NT)                                                                                                      \
     pull_indexed_kernel<NT><<<(int)blocks, kWave * kPullWaves, lds, (hipStream_t)stream>>>(                                         \
-        pp, recv_count, pull_offset, W, L * W, payload, idx_off, (idx_off / mi_ep_dispatch_row_bytes(H, quant_mode)) * (size_t)K,  \
+        pp, recv_count, pull_offset, W, L * W, pl, idx_off, (idx_off / mi_ep_dispatch_row_bytes(H, quant_mode)) * (size_t)K,  \
         (uint8_t *)recv_x, recv_x_scales, recv_src_idx, rows_hint, make_parity(epoch_ctr, 0, parity_stride), skip_src < 0 ? -1 : skip_src, \
         nt_from)
-    const int nt_from = pull_nt_from_row(rows_hint, payload);
+    const int nt_from = pull_nt_from_row(rows_hint, pl.data + pl.scales);
     if (nt_from != 0x7fffffff) MI_EP_PULL_INDEXED(true); else MI_EP_PULL_INDEXED(false);
 #undef MI_EP_PULL_INDEXED
     return launch_status();
@@ -1154,7 +1322,7 @@ extern "C" int mi_ep_dispatch_resolve_rows(const void *const *src_base_host, con
                                            size_t parity_stride, void *stream)
 {
     if (!src_base_host || !recv_count || !pull_offset || W <= 0 || W > MI_EP_MAX_RANKS || L <= 0 || H <= 0 || H % 16 || K <= 0 ||
-        K > MI_EP_MAX_TOPK || !row_offsets || !recv_src_idx || !a_base_out)
+        K > MI_EP_MAX_TOPK || !row_offsets || !recv_src_idx || !a_base_out || quant_is_mx(quant_mode))     // (MX: not for fused_deep_moe)
         return MI_EP_EINVAL;
     const size_t idx_off = mi_ep_dispatch_index_offset(H, quant_mode, K, region_bytes);
     if (idx_off == 0) return MI_EP_EINVAL;
@@ -1171,10 +1339,10 @@ extern "C" int mi_ep_dispatch_resolve_rows(const void *const *src_base_host, con
     if ((size_t)(hi - lo) + (epoch_ctr ? parity_stride : 0) + idx_off > 0xFFFFFFFFull) return MI_EP_ESIZE;
     *a_base_out = lo;
     if (rows_cap <= 0) return MI_EP_OK;
-    const int payload = H * (quant_mode == MI_EP_QUANT_NONE ? 2 : 1);
+    const RowPayload pl = row_payload(H, quant_mode);
     const int blocks = std::min((rows_cap + 255) / 256, 2048);
     resolve_rows_kernel<<<blocks, 256, (size_t)L * W * sizeof(int32_t), (hipStream_t)stream>>>(
-        pp, lo, recv_count, pull_offset, W, L * W, payload, idx_off, (idx_off / mi_ep_dispatch_row_bytes(H, quant_mode)) * (size_t)K, row_offsets,
+        pp, lo, recv_count, pull_offset, W, L * W, pl.data, idx_off, (idx_off / mi_ep_dispatch_row_bytes(H, quant_mode)) * (size_t)K, row_offsets,
         recv_x_scales, recv_src_idx, rows_cap, make_parity(epoch_ctr, 0, parity_stride));
     return launch_status();
 }
@@ -1185,22 +1353,22 @@ extern "C" int mi_ep_dispatch_pull_local(const void *my_rows, const void *topk_i
                                          int32_t *recv_src_idx, int32_t *local_row_out, const uint64_t *epoch_ctr, size_t parity_stride,
                                          void *stream)
 {
-    if (T < 0 || K <= 0 || K > MI_EP_MAX_TOPK || H <= 0 || H % 16 || E <= 0 || W <= 0 || W > MI_EP_MAX_RANKS || E % W || my_rank < 0 ||
-        my_rank >= W)
+    if (T < 0 || K <= 0 || K > MI_EP_MAX_TOPK || !dispatch_mode_ok(quant_mode, H) || E <= 0 || W <= 0 || W > MI_EP_MAX_RANKS || E % W ||
+        my_rank < 0 || my_rank >= W || (quant_is_mx(quant_mode) && !recv_x_scales))
         return MI_EP_EINVAL;
     if (T == 0 || rows_hint <= 0) return MI_EP_OK;               // a rank without tokens has nothing of its own to gather
     if (!my_rows || !topk_idx || !send_token_idx_small || !recv_count || !num_tokens_per_expert || !recv_x || !recv_src_idx)
         return MI_EP_EINVAL;
-    const int payload = H * (quant_mode == MI_EP_QUANT_NONE ? 2 : 1);
+    const RowPayload pl = row_payload(H, quant_mode);
     const int blocks = (T + kPullWaves - 1) / kPullWaves;
     const Parity par = make_parity(epoch_ctr, 0, parity_stride);
-    const int nt_from = pull_nt_from_row(rows_hint, payload);
+    const int nt_from = pull_nt_from_row(rows_hint, pl.data + pl.scales);
     const bool nt = nt_from != 0x7fffffff;
 #define MI_EP_PULL_LOCAL(I32)                                                                                                       \
     if (nt) MI_EP_PULL_LOCAL2(I32, true); else MI_EP_PULL_LOCAL2(I32, false)
 #define MI_EP_PULL_LOCAL2(I32, NT)                                                                                                  \
     pull_local_kernel<I32, NT><<<blocks, kWave * kPullWaves, 0, (hipStream_t)stream>>>(                                                \
-        (const uint8_t *)my_rows, topk_idx, send_token_idx_small, recv_count, num_tokens_per_expert, T, K, E, W, my_rank, payload, \
+        (const uint8_t *)my_rows, topk_idx, send_token_idx_small, recv_count, num_tokens_per_expert, T, K, E, W, my_rank, pl, \
         (uint8_t *)recv_x, recv_x_scales, recv_src_idx, rows_hint, par, nt_from, local_row_out)
     if (idx_is_i32) { MI_EP_PULL_LOCAL(true); } else { MI_EP_PULL_LOCAL(false); }
 #undef MI_EP_PULL_LOCAL
@@ -1213,17 +1381,15 @@ extern "C" int mi_ep_dispatch_stage_local(const void *x, const void *topk_idx, i
                                           int quant_mode, int rows_hint, void *recv_x, float *recv_x_scales, int32_t *recv_src_idx,
                                           int32_t *local_row_out, void *stream)
 {
-    if (T < 0 || K <= 0 || K > MI_EP_MAX_TOPK || H <= 0 || H % 16 || H > MI_EP_MAX_HIDDEN || E <= 0)
-        return MI_EP_EINVAL;
-    if (quant_mode != MI_EP_QUANT_NONE && quant_mode != MI_EP_QUANT_INT8 && quant_mode != MI_EP_QUANT_INT8_NOEPS &&
-        quant_mode != MI_EP_QUANT_FP8_E4M3)
+    if (T < 0 || K <= 0 || K > MI_EP_MAX_TOPK || !dispatch_mode_ok(quant_mode, H) || H > MI_EP_MAX_HIDDEN || E <= 0 ||
+        (quant_is_mx(quant_mode) && !recv_x_scales))
         return MI_EP_EINVAL;
     if (T == 0 || rows_hint <= 0) return MI_EP_OK;
     if (!x || !topk_idx || !send_token_idx_small || !recv_count || !num_tokens_per_expert || !recv_x || !recv_src_idx)
         return MI_EP_EINVAL;
-    const int payload = H * (quant_mode == MI_EP_QUANT_NONE ? 2 : 1);
+    const RowPayload pl = row_payload(H, quant_mode);
     const int blocks = (T + kStageWaves - 1) / kStageWaves;
-    const int nt_from = pull_nt_from_row(rows_hint, payload);
+    const int nt_from = pull_nt_from_row(rows_hint, pl.data + pl.scales);
     const bool nt = nt_from != 0x7fffffff;
 #define MI_EP_STAGE_LOCAL3(I32, QM, NT)                                                                                             \
     stage_local_kernel<I32, QM, NT><<<blocks, kWave * kStageWaves, 0, (hipStream_t)stream>>>(                                          \
@@ -1237,7 +1403,10 @@ extern "C" int mi_ep_dispatch_stage_local(const void *x, const void *topk_idx, i
         case MI_EP_QUANT_NONE: MI_EP_STAGE_LOCAL(MI_EP_QUANT_NONE); break;
         case MI_EP_QUANT_INT8: MI_EP_STAGE_LOCAL(MI_EP_QUANT_INT8); break;
         case MI_EP_QUANT_INT8_NOEPS: MI_EP_STAGE_LOCAL(MI_EP_QUANT_INT8_NOEPS); break;
-        default: MI_EP_STAGE_LOCAL(MI_EP_QUANT_FP8_E4M3); break;
+        case MI_EP_QUANT_FP8_E4M3: MI_EP_STAGE_LOCAL(MI_EP_QUANT_FP8_E4M3); break;
+        case MI_EP_QUANT_MXFP8_E4M3: MI_EP_STAGE_LOCAL(MI_EP_QUANT_MXFP8_E4M3); break;
+        case MI_EP_QUANT_MXFP8_E5M2: MI_EP_STAGE_LOCAL(MI_EP_QUANT_MXFP8_E5M2); break;
+        default: MI_EP_STAGE_LOCAL(MI_EP_QUANT_MXFP4_E2M1); break;
     }
 #undef MI_EP_STAGE_LOCAL
 #undef MI_EP_STAGE_LOCAL2
@@ -1443,11 +1612,12 @@ extern "C" int mi_ep_ll_wait_pack(const void *my_rows, const uint64_t *my_counts
                                   int32_t *src_info, int32_t *layout_range, int rows_capacity, const uint64_t *cur_epoch_word, uint64_t *epoch_ctr,
                                   size_t rows_parity_stride, int32_t *status, int timeout_ms, int max_blocks, void *stream)
 {
+    if (quant_is_mx(quant_mode)) return MI_EP_EINVAL;            // low-latency dispatch: quant modes 0-3 (include/mi_ep.h)
     if (!my_rows || !my_counts || !packed_recv_x || !packed_recv_count || !src_info || !layout_range || !cur_epoch_word || !epoch_ctr || !status ||
         W <= 0 || W > MI_EP_MAX_RANKS || L <= 0 || L * W > 2048 || H <= 0 || H % 16 || max_tokens <= 0)
         return MI_EP_EINVAL;
     const int cap = rows_capacity > 0 ? rows_capacity : L * W * max_tokens;
-    const int payload = H * (quant_mode == MI_EP_QUANT_NONE ? 2 : 1);
+    const RowPayload pl = row_payload(H, quant_mode);
     // the waves of this launch WAIT for rows: at most 512 workgroups (a quarter of the chip's slots), the rows are grid-strided
     long long blocks = ((long long)L * W * max_tokens + kPullRowsPerBlock - 1) / kPullRowsPerBlock;
     // MI_EP_LL_WAIT_BLOCKS (measurement / shared-GPU setups): with two PROCESSES on one GPU, 512 waiting workgroups of one (two on every CU) keep
@@ -1459,7 +1629,7 @@ extern "C" int mi_ep_ll_wait_pack(const void *my_rows, const uint64_t *my_counts
     if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;      // (the caller knows that ranks share this GPU)
     if (blocks < 1) blocks = 1;
     ll_wait_pack_kernel<<<(int)blocks, kWave * kPullWaves, (size_t)(L * W + 16) * 4, (hipStream_t)stream>>>(
-        (const uint8_t *)my_rows, my_counts, counts_parity_stride, rows_parity_stride, cur_epoch_word, epoch_ctr, max_tokens, W, L, payload, count_type,
+        (const uint8_t *)my_rows, my_counts, counts_parity_stride, rows_parity_stride, cur_epoch_word, epoch_ctr, max_tokens, W, L, pl.data, count_type,
         (uint8_t *)packed_recv_x, packed_recv_x_scales, src_info, layout_range, packed_recv_count, cap, status,
         (uint64_t)(timeout_ms > 0 ? timeout_ms : 10000) * 100000ull);
     return launch_status();
@@ -1471,17 +1641,18 @@ extern "C" int mi_ep_ll_pack(const void *my_rows, const int32_t *layout_range, i
                              void *packed_recv_x, float *packed_recv_x_scales, int32_t *src_info, int rows_capacity, const uint64_t *epoch_ctr,
                              size_t rows_parity_stride, void *stream)
 {
+    if (quant_is_mx(quant_mode)) return MI_EP_EINVAL;            // low-latency dispatch: quant modes 0-3 (include/mi_ep.h)
     if (!my_rows || !layout_range || !packed_recv_x || !src_info || W <= 0 || W > MI_EP_MAX_RANKS || L <= 0 || L * W > 2048 || H <= 0 || H % 16 ||
         max_tokens <= 0)
         return MI_EP_EINVAL;
     PeerPtrs pp;
     for (int i = 0; i < W; ++i) pp.p[i] = const_cast<void *>(my_rows);
     const int cap = rows_capacity > 0 ? rows_capacity : L * W * max_tokens;      // rows the caller's output buffers hold
-    const int payload = H * (quant_mode == MI_EP_QUANT_NONE ? 2 : 1);
+    const RowPayload pl = row_payload(H, quant_mode);
     long long blocks = ((long long)L * W * max_tokens + kPullRowsPerBlock - 1) / kPullRowsPerBlock;
     if (blocks > 256 * 8) blocks = 256 * 8;
     if (blocks < 1) blocks = 1;
-    pull_kernel<<<(int)blocks, kWave * kPullWaves, (size_t)L * W * 4, (hipStream_t)stream>>>(pp, layout_range, nullptr, max_tokens, W, L * W, payload,
+    pull_kernel<<<(int)blocks, kWave * kPullWaves, (size_t)L * W * 4, (hipStream_t)stream>>>(pp, layout_range, nullptr, max_tokens, W, L * W, pl,
                                                                                          (uint8_t *)packed_recv_x, packed_recv_x_scales, src_info,
                                                                                          cap, make_parity(epoch_ctr, 0, rows_parity_stride));
     return launch_status();
@@ -1506,6 +1677,7 @@ extern "C" int mi_ep_ll_dispatch_recv(const void *my_rows, const uint64_t *my_co
                                       float *packed_recv_x_scales, int64_t *packed_recv_count, int32_t *src_info,
                                       int32_t *layout_range, int rows_capacity, int32_t *status, int timeout_ms, void *stream)
 {
+    if (quant_is_mx(quant_mode)) return MI_EP_EINVAL;            // low-latency dispatch: quant modes 0-3 (include/mi_ep.h)
     if (!my_rows || !my_counts || !packed_recv_x || !packed_recv_count || !src_info || !layout_range || !status ||
         W <= 0 || W > MI_EP_MAX_RANKS || L <= 0 || L * W > 2048 || H <= 0 || H % 16 || max_tokens <= 0 || epoch == 0)
         return MI_EP_EINVAL;
@@ -1517,7 +1689,7 @@ extern "C" int mi_ep_ll_dispatch_recv(const void *my_rows, const uint64_t *my_co
     const int cap = rows_capacity > 0 ? rows_capacity : L * W * max_tokens;      // rows the caller's output buffers hold
     PeerPtrs pp;
     for (int i = 0; i < W; ++i) pp.p[i] = const_cast<void *>(my_rows);
-    const int payload = H * (quant_mode == MI_EP_QUANT_NONE ? 2 : 1);
+    const RowPayload pl = row_payload(H, quant_mode);
     // worst case rows = W * max_tokens * min(K, L) is not known here (K); size the grid for W * max_tokens rows per
     // 16-row block, capped: the kernel grid-strides over the device-side total.
     // worst case rows = every (local expert, source) slab full; the kernel grid-strides over the device-side total, so
@@ -1526,7 +1698,7 @@ extern "C" int mi_ep_ll_dispatch_recv(const void *my_rows, const uint64_t *my_co
     if (blocks > 256 * 8) blocks = 256 * 8;
     if (blocks < 1) blocks = 1;
     pull_kernel<<<(int)blocks, kWave * kPullWaves, (size_t)L * W * 4, s>>>(pp, layout_range, nullptr, max_tokens, W, L * W,
-                                                                         payload, (uint8_t *)packed_recv_x,
+                                                                         pl, (uint8_t *)packed_recv_x,
                                                                          packed_recv_x_scales, src_info, cap,
                                                                          Parity{EpochRef{nullptr, 0}, 0});
     return launch_status();
@@ -1539,6 +1711,7 @@ extern "C" int mi_ep_ll_post_recv(uint64_t *const *peer_counts_host, const int32
                                   uint64_t *epoch_ctr, size_t rows_parity_stride, size_t counts_parity_stride, int32_t *status,
                                   int timeout_ms, void *stream)
 {
+    if (quant_is_mx(quant_mode)) return MI_EP_EINVAL;            // low-latency dispatch: quant modes 0-3 (include/mi_ep.h)
     if (!peer_counts_host || !num_tokens_per_expert || !my_rows || !my_counts || !packed_recv_x || !packed_recv_count || !src_info ||
         !layout_range || !status || W <= 0 || W > MI_EP_MAX_RANKS || my_rank < 0 || my_rank >= W || L <= 0 || L * W > 2048 || H <= 0 ||
         H % 16 || max_tokens <= 0 || (epoch == 0 && !epoch_ctr))
@@ -1558,11 +1731,11 @@ extern "C" int mi_ep_ll_post_recv(uint64_t *const *peer_counts_host, const int32
                                                             epoch_ctr ? counts_parity_stride : 0, epoch_ctr, L, W, count_type,
                                                             layout_range, packed_recv_count, status, ticks);
     const int cap = rows_capacity > 0 ? rows_capacity : L * W * max_tokens;      // rows the caller's output buffers hold
-    const int payload = H * (quant_mode == MI_EP_QUANT_NONE ? 2 : 1);
+    const RowPayload pl = row_payload(H, quant_mode);
     long long blocks = ((long long)L * W * max_tokens + kPullRowsPerBlock - 1) / kPullRowsPerBlock;
     if (blocks > 256 * 8) blocks = 256 * 8;
     if (blocks < 1) blocks = 1;
-    pull_kernel<<<(int)blocks, kWave * kPullWaves, (size_t)L * W * 4, s>>>(pp, layout_range, nullptr, max_tokens, W, L * W, payload,
+    pull_kernel<<<(int)blocks, kWave * kPullWaves, (size_t)L * W * 4, s>>>(pp, layout_range, nullptr, max_tokens, W, L * W, pl,
                                                                          (uint8_t *)packed_recv_x, packed_recv_x_scales, src_info, cap,
                                                                          make_parity(epoch_ctr, 0, rows_parity_stride));
     return launch_status();

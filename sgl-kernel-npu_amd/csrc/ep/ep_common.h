@@ -37,6 +37,29 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float bf16_to_f32(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
 
+// Bytes of one dispatched row per quant mode (include/mi_ep.h): `data` = the elements (a multiple of 16 for every valid H), `scales` =
+// the E8M0 block scales of the MX modes (0 otherwise).  A staged row is data | scales | pad | meta; the receive side stores data to
+// recv_x row r (`data` bytes apart) and scales to recv_x_scales + r * scales.  Every staging, pull, push and unpack path sizes its
+// rows from here.
+__host__ __device__ constexpr bool quant_is_mx(int qm) { return qm >= MI_EP_QUANT_MXFP8_E4M3 && qm <= MI_EP_QUANT_MXFP4_E2M1; }
+struct RowPayload {
+    int data, scales;
+    __host__ __device__ int meta_off() const { return (data + scales + 15) & ~15; }     // the 16-byte meta words
+    __host__ __device__ size_t stride() const { return MI_EP_ROW_STRIDE(data + scales); }  // >= meta_off() + 16
+};
+__host__ __device__ inline RowPayload row_payload(int H, int qm)
+{
+    if (qm == MI_EP_QUANT_NONE) return RowPayload{2 * H, 0};
+    if (qm == MI_EP_QUANT_MXFP4_E2M1) return RowPayload{H / 2, H / 32};
+    if (quant_is_mx(qm)) return RowPayload{H, H / 32};
+    return RowPayload{H, 0};
+}
+// quant modes the normal-dispatch stage / receive entry points accept, and the hidden sizes they take in that mode
+inline bool dispatch_mode_ok(int qm, int H)
+{
+    return qm >= MI_EP_QUANT_NONE && qm <= MI_EP_QUANT_MXFP4_E2M1 && H > 0 && H % (quant_is_mx(qm) ? 32 : 16) == 0;
+}
+
 // float -> bf16 bits, round to nearest even; NaN -> 0x7FC0 (same as torch / the CPU oracle)
 __device__ __forceinline__ uint32_t f32_to_bf16_rne(float f)
 {

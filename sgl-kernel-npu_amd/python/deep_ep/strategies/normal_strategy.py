@@ -45,6 +45,11 @@ def _event(e):
     return getattr(e, "event", None)
 
 
+def _bytes(t):
+    """Rows of one-byte elements as uint8 (index_copy_ does not take the FP8 / FP4 / E8M0 dtypes of the MX modes)."""
+    return t.view(torch.uint8) if t.dim() == 2 and t.element_size() == 1 else t
+
+
 def long_seq_rounds():
     """(rounds, tokens per round) of the reference's long-sequence mode (csrc/deepep/deep_ep.cpp:63-90, README.md:224-226):
     DEEPEP_NORMAL_LONG_SEQ_ROUND in [1, 256], DEEPEP_NORMAL_LONG_SEQ_PER_ROUND_TOKENS in [32, 8192], product <= 131072."""
@@ -125,6 +130,8 @@ class DefaultNormalCommStrategy(NormalEPCommStrategy):
             # MOE_EXPERT_TOKEN_NUMS_TYPE=0)
             cumulative = int(os.getenv("MOE_EXPERT_TOKEN_NUMS_TYPE", "1")) == 0
             n = (int(lst[-1]) if cumulative else int(sum(lst))) if lst else 0
+            # scales: f32 [rows] per token, or E8M0 [rows * H/32] per block (MX modes), re-assembled row by row
+            rs = rs.view(rx.size(0), -1) if use_quant and quant_type.startswith("mx_") else rs
             chunks.append(dict(t0=t0, n=n, rx=rx[:n], rs=rs[:n], src=src_idx[:3 * n].view(n, 3), cnt=cnt, src_idx=src_idx,
                                send_head=send_head, topk_idx=ti, topk_weights=wi))
             lists.append(lst)
@@ -134,7 +141,7 @@ class DefaultNormalCommStrategy(NormalEPCommStrategy):
         N = sum(c["n"] for c in chunks)
         rows = max(N, 1)
         recv_x = torch.empty((rows,) + tuple(chunks[0]["rx"].shape[1:]), dtype=chunks[0]["rx"].dtype, device=dev)
-        recv_scales = torch.empty((rows,), dtype=torch.float32, device=dev)
+        recv_scales = torch.empty((rows,) + tuple(chunks[0]["rs"].shape[1:]), dtype=chunks[0]["rs"].dtype, device=dev)
         recv_src = torch.empty((rows, 3), dtype=torch.int32, device=dev)
         running = torch.zeros_like(total_cnt)
         seg_ids = torch.arange(E, device=dev)
@@ -144,8 +151,8 @@ class DefaultNormalCommStrategy(NormalEPCommStrategy):
             excl = torch.cumsum(c["cnt"], 0) - c["cnt"]
             dest = final_excl[seg] + running[seg] + (torch.arange(n, device=dev) - excl[seg])
             running = running + c["cnt"]
-            recv_x.index_copy_(0, dest, c["rx"])
-            recv_scales.index_copy_(0, dest, c["rs"])
+            _bytes(recv_x).index_copy_(0, dest, _bytes(c["rx"]))
+            _bytes(recv_scales).index_copy_(0, dest, _bytes(c["rs"]))
             src = c["src"].clone()
             src[:, 1] += c["t0"]                               # token index inside the whole batch
             recv_src.index_copy_(0, dest, src)
@@ -157,7 +164,7 @@ class DefaultNormalCommStrategy(NormalEPCommStrategy):
         handle = (rpm, cpm, rcpm, final_src_idx, is_token_in_rank, final_cum.to(torch.int32), topk_idx, topk_weights)
         recv_topk_idx = torch.empty((N, topk_idx.size(1)), dtype=topk_idx.dtype, device=dev)
         recv_topk_weights = torch.empty((N, topk_idx.size(1)), dtype=topk_weights.dtype, device=dev)
-        return ((recv_x, recv_scales) if use_quant else recv_x, recv_topk_idx, recv_topk_weights, counts, handle,
+        return ((recv_x, recv_scales.reshape(-1)) if use_quant else recv_x, recv_topk_idx, recv_topk_weights, counts, handle,
                 EventOverlap(None))
 
     def combine(self, x, handle, topk_weights=None, bias=None, config=None, previous_event=None, async_finish=False,
@@ -218,8 +225,9 @@ class AlltoAllNormalCommStrategy(NormalEPCommStrategy):
                  topk_idx, topk_weights, expert_alignment=1, num_worst_tokens=0, config=None, previous_event=None,
                  async_finish=False, allocate_on_comm_stream=False, dispatch_wait_recv_cost_stats=None, quant_mode=None):
         data, quant_type, use_quant = resolve_quant(x, quant_mode)
-        if quant_type not in ("bf16", "int8", "pertoken_fp8_e4m3"):
-            raise ValueError(f"{quant_type} is not supported on this device, please use int8 or bf16 instead.")
+        if quant_type not in ("bf16", "int8", "pertoken_fp8_e4m3", "mx_fp8_e4m3", "mx_fp8_e5m2", "mx_fp4_e2m1"):
+            raise ValueError(f"{quant_type} is not supported on this device, please use int8, pertoken_fp8_e4m3, mx_fp8_e4m3, "
+                             "mx_fp8_e5m2, mx_fp4_e2m1 or bf16 instead.")
         if handle is not None:
             raise NotImplementedError("Optional communication handle is not supported yet.")
         assert num_tokens_per_rank is not None and is_token_in_rank is not None and num_tokens_per_expert is not None

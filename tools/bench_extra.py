@@ -22,11 +22,41 @@ def ev_time(fn, n=30, warm=5):
     b.record(); torch.cuda.synchronize()
     return {"p50_us": ts[len(ts) // 2], "p99_us": ts[min(len(ts) - 1, int(len(ts) * 0.99))], "min_us": ts[0], "queued_us": a.elapsed_time(b) * 1e3 / 50}
 
+def dispatch_mx(buf, g):
+    """Normal dispatch at the C2 shape per rank (4096 x 7168, top-8 of 256, W = 1) in INT8 and the three MX modes: get_dispatch_layout +
+    dispatch p50 / queued, GB/s on the algorithmic bytes (x read once, every received row's payload + scales + triple written), and the
+    runtime's per-launch profile (dispatch_stage_local = the quantising kernel at one rank)."""
+    T, H, K, E = 4096, 7168, 8, 256
+    x = torch.randn((T, H), generator=g, device="cuda").to(torch.bfloat16)
+    idx = torch.topk(torch.rand((T, E), generator=g, device="cuda"), K, dim=-1)[1]
+    w = torch.rand((T, K), generator=g, device="cuda")
+    row_bytes = {"int8": H + 4, "mx_fp8_e4m3": H + H // 32, "mx_fp8_e5m2": H + H // 32, "mx_fp4_e2m1": H // 2 + H // 32}
+    res = {}
+    for mode, rb in row_bytes.items():
+        def f():
+            per_rank, _, per_expert, is_in, _ = buf.get_dispatch_layout(idx, E)
+            return buf.dispatch(x, num_tokens_per_rank=per_rank, is_token_in_rank=is_in, num_tokens_per_expert=per_expert, topk_idx=idx,
+                                topk_weights=w, quant_mode=mode)
+        rows = sum(f()[3])
+        buf.begin_profile(0, 20, "")
+        for _ in range(20): f()
+        buf.end_profile()
+        prof = {k: ms / n * 1e3 for k, (n, ms) in buf.get_profile_summary().items()}
+        t = ev_time(f)
+        nbytes = T * H * 2 + rows * (rb + 12)
+        res[mode] = dict(t, rows=rows, bytes=nbytes, GBps=nbytes / t["p50_us"] / 1e3, GBps_queued=nbytes / t["queued_us"] / 1e3,
+                         kernels_avg_us=prof)
+    return res
+
 def main():
     torch.cuda.set_device(0)
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29533")
     dist.init_process_group("gloo", rank=0, world_size=1)
     import deep_ep, sgl_kernel_npu
+    if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "dispatch_mx":      # this section alone
+        buf = deep_ep.Buffer(dist.group.WORLD, low_latency_mode=True)
+        print(json.dumps({"dispatch_mx": dispatch_mx(buf, torch.Generator(device="cuda").manual_seed(0))}))
+        return
     from sgl_kernel_npu.activation.swiglu_quant import swiglu_quant
     from sgl_kernel_npu.norm.add_rmsnorm_bias import add_rmsnorm_bias
     from sgl_kernel_npu.norm.split_qkv_rmsnorm_rope import split_qkv_rmsnorm_rope
@@ -241,6 +271,7 @@ def main():
                                      quant_mode="per_tensor_quant_asymm", q_out0=q0, kv_cache_out0=kv, q_out1=q1, kv_cache_out1=kr)
     t = ev_time(f_cold, n=36, warm=12)
     out["mla_preprocess_128tok_cold_weights"] = dict(t, weight_GBps=wbytes / t["p50_us"] / 1e3)
+    out["dispatch_mx"] = dispatch_mx(buf, g)
     for v in out.values():      # bandwidth at the queued rate beside the single-call one
         if isinstance(v, dict) and v.get("GBps") and v.get("queued_us") and v.get("p50_us"):
             v["GBps_queued"] = v["GBps"] * v["p50_us"] / v["queued_us"]
