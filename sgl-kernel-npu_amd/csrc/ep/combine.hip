@@ -221,7 +221,7 @@ __device__ __forceinline__ void combine_reduce_body(
     __amdgpu_buffer_rsrc_t rs[FLAGGED ? KMAX : 1];
     if constexpr (FLAGGED) {
 #pragma unroll
-        for (int k = 0; k < KMAX; ++k) rs[k] = sys_row_rsrc(rowp[k], H * 2);
+        for (int k = 0; k < KMAX; ++k) rs[k] = row_rsrc(rowp[k], H * 2);
     }
     auto chunk = [&](int c, auto all_tag) {
         constexpr bool ALL = decltype(all_tag)::value;
@@ -325,14 +325,10 @@ __global__ __launch_bounds__(256) void combine_pack_kernel(const uint8_t *__rest
     const int lane = lane_id(), wave = threadIdx.x / kWave, nw = blockDim.x / kWave;
     const int n16 = row_bytes / 16;
     for (long long r = (long long)blockIdx.x * nw + wave; r < total; r += (long long)gridDim.x * nw) {
-        int lo = 0, hi = LW - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (cum[mid] > r) hi = mid; else lo = mid + 1;
-        }
-        const int j = (int)(r - (lo ? cum[lo - 1] : 0));
+        const int i = seg_of(cum, LW, r);
+        const int j = (int)(r - (i ? cum[i - 1] : 0));
         const u32x4 *s16 = (const u32x4 *)(x + (size_t)r * row_bytes);
-        u32x4 *d16 = (u32x4 *)(packed + ((size_t)dstoff[lo] + j) * row_bytes);
+        u32x4 *d16 = (u32x4 *)(packed + ((size_t)dstoff[i] + j) * row_bytes);
         for (int base = 0; base < n16; base += kWave * 8) {
             u32x4 v[8];
 #pragma unroll
@@ -378,10 +374,7 @@ static int combine_push_launch(const void *x, const int32_t *src_idx, const int3
     if (rows_hint <= 0 && !tail) return MI_EP_OK;
     if (rows_hint > 0 && (!x || !src_idx)) return MI_EP_EINVAL;
     PeerPtrs pp;
-    for (int i = 0; i < W; ++i) {
-        if (!dst_base_host[i]) return MI_EP_EINVAL;
-        pp.p[i] = dst_base_host[i];
-    }
+    if (!peer_ptrs(dst_base_host, W, pp)) return MI_EP_EINVAL;
     long long blocks = ((long long)std::max(rows_hint, 1) + kPushWaves - 1) / kPushWaves;        // one row per wave until the chip is full
     static const long long cap = getenv("MI_EP_PUSH_BLOCKS") ? atoll(getenv("MI_EP_PUSH_BLOCKS")) : 256 * 8;
     if (blocks > cap) blocks = cap;
@@ -419,10 +412,7 @@ extern "C" int mi_ep_combine_push_signal_wait(const void *x, const int32_t *src_
     PushTail tail{};
     tail.arrive = arrive_word, tail.my_flags = my_flags, tail.epoch_bump = epoch_ctr, tail.status = status;
     tail.timeout_ticks = (uint64_t)(timeout_ms > 0 ? timeout_ms : 10000) * 100000ull;
-    for (int i = 0; i < W; ++i) {
-        if (!peer_flags_host[i]) return MI_EP_EINVAL;
-        tail.flag_peers.p[i] = peer_flags_host[i];
-    }
+    if (!peer_ptrs(peer_flags_host, W, tail.flag_peers)) return MI_EP_EINVAL;
     return combine_push_launch(x, src_idx, total_rows_dev, rows_hint, H, K, dst_base_host, W, slot_region_bytes, epoch_ctr, parity_stride, my_rank,
                                local_row, &tail, stream);
 }
@@ -442,10 +432,7 @@ extern "C" int mi_ep_combine_push_flagged(const void *x, const int32_t *src_idx,
     slot_region_bytes = slot_region_bytes ? std::min(slot_region_bytes, flagged_bytes) : flagged_bytes;
     PushTail tail{};
     tail.epoch_bump = const_cast<uint64_t *>(epoch_ctr), tail.row_flags_parity_stride = row_flags_parity_stride, tail.cur_epoch = cur_epoch_word;
-    for (int i = 0; i < W; ++i) {
-        if (!peer_row_flags_host[i]) return MI_EP_EINVAL;
-        tail.row_flag_peers.p[i] = peer_row_flags_host[i];
-    }
+    if (!peer_ptrs(peer_row_flags_host, W, tail.row_flag_peers)) return MI_EP_EINVAL;
     return combine_push_launch(x, src_idx, total_rows_dev, rows_hint, H, K, dst_base_host, W, slot_region_bytes, epoch_ctr, parity_stride, my_rank,
                                local_row, &tail, stream);
 }

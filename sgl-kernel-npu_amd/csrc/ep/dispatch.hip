@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "ep_common.h"
 #include "layout_dev.h"
@@ -93,13 +94,6 @@ __device__ __forceinline__ void route(const LLGeom &ll, int e, int small, const 
 // send_token_idx_small holds -- from a copy of the batch's routing table in LDS (<= 8192 ids; every workgroup loads it once, one id
 // per thread), 64 pairs per step: compare, ballot, popcount.  No wave waits for the layout workgroup; the row is loaded and quantised
 // first, so the count runs under the row's memory latency.
-// buffer descriptor over one window row (wave-uniform base): the write-through stores of the one-launch low-latency form go through it
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(void *row, int bytes)
-{
-    const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uint64_t)(uintptr_t)row >> 32)) << 32) |
-                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)row);
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)base, 0, bytes, 0x00020000);
-}
 struct LateIdx {
     const int32_t *ids;        // LDS: expert id of pair p = t * K + k, -1 = no selection; NULL: the layout ran in an earlier launch
     int kpart;                 // the selection this wave sends
@@ -131,7 +125,7 @@ __device__ __forceinline__ void route_token(const LLGeom &ll, const void *topk_i
 // ---------------------------------------------------------------------------------------------
 // stage, INT8: item = 16 consecutive elements = two 16-B loads -> one 16-B store
 // ---------------------------------------------------------------------------------------------
-// Row load and quantisation, shared by every kernel that quantises a token row (stage_int8_body, stage_local_kernel): the rounding
+// Row load and quantisation, shared by every kernel that quantises a token row (stage_body, stage_local_kernel): the rounding
 // exists once.  Item it * kWave + lane of row t; items past H / 16 are zero (they take part in the maximum).
 __device__ __forceinline__ void ld_row_items(const uint16_t *__restrict__ x, int t, int H, u32x4 (&raw)[kMaxItems][2])
 {
@@ -294,24 +288,19 @@ __device__ __forceinline__ void st_block_scales(uint8_t *sc_row, int it, uint32_
         sc_row[b] = (uint8_t)s;
     }
 }
-// One quantised row: items (16 B per lane; MXFP4 8 B) to `row`, MX block scales to sc_row (see st_block_scales).  Called by the whole wave.
-template <int QM, bool NT>
-__device__ __forceinline__ void st_quant_row(uint8_t *row, uint8_t *sc_row, bool sc_dw, int H, const u32x4 (&q)[kMaxItems],
+// One row held by the wave, N items per lane (bf16: 16-byte chunks; quantised: 16 elements, 16 B each, MXFP4 8 B), through the store
+// policy `st` (StMem / StWT, ep_common.h); MX block scales to sc_row (see st_block_scales).  Called by the whole wave.
+template <int QM, class St, int N>
+__device__ __forceinline__ void st_quant_row(const St &st, uint8_t *sc_row, bool sc_dw, int H, const u32x4 (&q)[N],
                                              const uint32_t (&sc)[kMaxItems], int lane)
 {
-    const int nitems = H / 16;
+    const int nitems = QM == MI_EP_QUANT_NONE ? H / 8 : H / 16;
 #pragma unroll
-    for (int it = 0; it < kMaxItems; ++it) {
+    for (int it = 0; it < N; ++it) {
         const int item = it * kWave + lane;
         if (item < nitems) {
-            if constexpr (QM == MI_EP_QUANT_MXFP4_E2M1) {
-                const u32x2 v = u32x2{q[it][0], q[it][1]};
-                if (NT) __builtin_nontemporal_store(v, (u32x2 *)row + item);
-                else ((u32x2 *)row)[item] = v;
-            } else {
-                if (NT) __builtin_nontemporal_store(q[it], (u32x4 *)row + item);
-                else ((u32x4 *)row)[item] = q[it];
-            }
+            if constexpr (QM == MI_EP_QUANT_MXFP4_E2M1) st(item, u32x2{q[it][0], q[it][1]});
+            else st(item, q[it]);
         }
     }
     if constexpr (quant_is_mx(QM)) {
@@ -319,107 +308,6 @@ __device__ __forceinline__ void st_quant_row(uint8_t *row, uint8_t *sc_row, bool
         for (int it = 0; it < kMaxItems; ++it)
             if (it * kWave < nitems) st_block_scales(sc_row, it, sc[it], H / 32, sc_dw, lane);     // wave-uniform condition
     }
-}
-template <bool I32, int QM, bool LATE>
-__device__ __forceinline__ void stage_int8_body(
-    const uint16_t *__restrict__ x, const void *__restrict__ topk_idx, const int32_t *__restrict__ idx_small,
-    const int32_t *__restrict__ send_off, int T, int K, int H, int E, int my_rank, const PeerPtrs &dsts, const LLGeom &ll, int ksplit,
-    size_t idx_off, const PushGeom &pg, const Parity &par, const int wid, const LateIdx &late)
-{
-    const int lane = lane_id();
-    // ksplit waves share a token (decode-size batches: every wave re-reads the row from L2 and writes K / ksplit copies)
-    const int t = wid / ksplit, kpart = wid - t * ksplit;
-    if (t >= T) return;
-    const int nitems = H / 16;
-    constexpr bool kMx = quant_is_mx(QM);
-    const RowPayload pl = row_payload(H, QM);
-    const size_t stride = pl.stride();
-    // the row is requested before the routing is known (a token that selects nothing is the rare case): behind the routing's two
-    // dependent loads (expert id, then slot and segment offset) the 14 KB of the row started one to two round trips late
-    u32x4 raw[kMaxItems][2];
-    ld_row_items(x, t, H, raw);
-    // routing of this token: lane k < K owns pair (t,k)
-    long long e_l = -1;
-    int slot_l = 0, dst_l = 0;
-    if (lane < K) {
-        e_l = ld_idx<I32>(topk_idx, (long long)t * K + lane);
-        if (e_l < 0 || e_l >= E) e_l = -1;
-    }
-    if (!LATE) route_token<I32, false>(ll, topk_idx, idx_small, send_off, t, K, E, my_rank, late, e_l, slot_l, dst_l);
-    const unsigned long long vmask = __ballot(e_l >= 0);
-    if (vmask == 0ull) return;      // token selects nothing: no row is produced
-    float scale_out = 0.f;                              // MX modes: the meta's scale word is 0
-    u32x4 q[kMaxItems];
-    uint32_t sc[kMaxItems];
-    if constexpr (kMx) quant_row_mx<QM>(raw, q, sc);
-    else quant_row<QM>(raw, q, scale_out);
-    if (LATE) route_token<I32, true>(ll, topk_idx, idx_small, send_off, t, K, E, my_rank, late, e_l, slot_l, dst_l);
-    if (idx_off) {
-        // compact staging (normal-mode pull transport): the row is written ONCE at slot t; the expert-sorted index tells the
-        // receivers which token row each of their rows is (K-fold less staging traffic than one copy per (t, k)).
-        // Push transport: the same row + index entries, written into every destination rank's window instead of the own one.
-        stage_token_rows(pg, dsts, parity_off(par), idx_off, my_rank, t, K, e_l, slot_l, send_off, [&](uint8_t *base) {
-            uint8_t *row = base + (size_t)t * stride;
-            if constexpr (kMx) {
-                st_quant_row<QM, false>(row, row + pl.data, true, H, q, sc, lane);
-            } else {
-                u32x4 *dst = (u32x4 *)row;
-#pragma unroll
-                for (int it = 0; it < kMaxItems; ++it) {
-                    const int item = it * kWave + lane;
-                    if (item < nitems) dst[item] = q[it];
-                }
-            }
-            if (lane == 0) *(u32x4 *)(row + pl.meta_off()) = u32x4{__float_as_uint(scale_out), (uint32_t)t, 0u, (uint32_t)my_rank};
-        });
-        return;
-    }
-    const size_t poff = parity_off(par);
-    for (int k = kpart; k < K; k += ksplit) {
-        if (!((vmask >> k) & 1ull)) continue;          // wave-uniform
-        const int slot = __builtin_amdgcn_readlane(slot_l, k);      // k is wave-uniform: v_readlane instead of an LDS round trip
-        const int drank = __builtin_amdgcn_readlane(dst_l, k);
-        uint8_t *row = (uint8_t *)dsts.p[drank] + poff + (size_t)slot * stride;
-        const u32x4 meta = u32x4{__float_as_uint(scale_out), (uint32_t)t, (uint32_t)k, (uint32_t)my_rank};
-        if (LATE) {
-            // one-launch low-latency form: the rows are announced to their owners from INSIDE this launch (ll_layout_send_kernel's tail), so
-            // they are written through the caches (sc0 sc1) -- the announcing workgroup then needs no release fence, only every wave's drain
-            const __amdgpu_buffer_rsrc_t d = row_rsrc(row, H + MI_EP_ROW_META_BYTES);
-#pragma unroll
-            for (int it = 0; it < kMaxItems; ++it) {
-                const int item = it * kWave + lane;
-                if (item < nitems) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wt_u32x4, q[it]), d, item * 16, 0, 17);
-            }
-            u32x4 m = meta;
-            if (late.tag) {                                 // tagged rows: the payload is at its owner before the meta word says so
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                m[3] = (uint32_t)my_rank | (late.tag << 8);
-            }
-            if (lane == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wt_u32x4, m), d, H, 0, 17);
-            continue;
-        }
-        if constexpr (kMx) {
-            st_quant_row<QM, false>(row, row + pl.data, true, H, q, sc, lane);
-        } else {
-            u32x4 *dst = (u32x4 *)row;
-#pragma unroll
-            for (int it = 0; it < kMaxItems; ++it) {
-                const int item = it * kWave + lane;
-                if (item < nitems) dst[item] = q[it];
-            }
-        }
-        if (lane == 0) *(u32x4 *)(row + pl.meta_off()) = meta;
-    }
-}
-
-template <bool I32, int QM>
-__global__ __launch_bounds__(kWave * kStageWaves) void stage_int8_kernel(
-    const uint16_t *__restrict__ x, const void *__restrict__ topk_idx, const int32_t *__restrict__ idx_small,
-    const int32_t *__restrict__ send_off, int T, int K, int H, int E, int my_rank, PeerPtrs dsts, LLGeom ll, int ksplit, size_t idx_off,
-    PushGeom pg, Parity par)
-{
-    stage_int8_body<I32, QM, false>(x, topk_idx, idx_small, send_off, T, K, H, E, my_rank, dsts, ll, ksplit, idx_off, pg, par,
-                                    (int)(blockIdx.x * kStageWaves + threadIdx.x / kWave), LateIdx{nullptr, 0, 0u});
 }
 
 // stage, BF16 (no quantisation): item = one 16-B chunk
@@ -435,18 +323,28 @@ __device__ __forceinline__ void ld_row_chunks(const uint16_t *__restrict__ x, in
         if (item < nitems) raw[it] = src[item];
     }
 }
-template <bool I32, bool LATE>
-__device__ __forceinline__ void stage_bf16_body(
+
+// Staging of one token row by one wave, every quant mode: load (and quantise) the row, route it, store it with its meta
+// {scale, t, k, src_rank} -- compact / push staging (idx_off != 0), else one copy per selection; LATE: the one-launch low-latency form.
+template <bool I32, int QM, bool LATE>
+__device__ __forceinline__ void stage_body(
     const uint16_t *__restrict__ x, const void *__restrict__ topk_idx, const int32_t *__restrict__ idx_small,
     const int32_t *__restrict__ send_off, int T, int K, int H, int E, int my_rank, const PeerPtrs &dsts, const LLGeom &ll, int ksplit,
     size_t idx_off, const PushGeom &pg, const Parity &par, const int wid, const LateIdx &late)
 {
+    constexpr bool kBf16 = QM == MI_EP_QUANT_NONE, kMx = quant_is_mx(QM);
     const int lane = lane_id();
     // ksplit waves share a token (decode-size batches: every wave re-reads the row from L2 and writes K / ksplit copies)
     const int t = wid / ksplit, kpart = wid - t * ksplit;
     if (t >= T) return;
-    const int nitems = H / 8;
-    const size_t stride = MI_EP_ROW_STRIDE((size_t)H * 2);
+    const RowPayload pl = row_payload(H, QM);
+    const size_t stride = pl.stride();
+    // quantised modes: the row is requested before the routing is known (a token that selects nothing is the rare case): behind the
+    // routing's two dependent loads (expert id, then slot and segment offset) the 14 KB of the row started one to two round trips late.
+    // bf16 loads its row after the routing: its 16 chunks per lane held across the routing would raise the kernel's VGPRs further.
+    u32x4 raw[kBf16 ? 1 : kMaxItems][2];
+    if constexpr (!kBf16) ld_row_items(x, t, H, raw);
+    // routing of this token: lane k < K owns pair (t,k)
     long long e_l = -1;
     int slot_l = 0, dst_l = 0;
     if (lane < K) {
@@ -455,54 +353,57 @@ __device__ __forceinline__ void stage_bf16_body(
     }
     if (!LATE) route_token<I32, false>(ll, topk_idx, idx_small, send_off, t, K, E, my_rank, late, e_l, slot_l, dst_l);
     const unsigned long long vmask = __ballot(e_l >= 0);
-    if (vmask == 0ull) return;
-    constexpr int kIt = kChunkItems;
-    u32x4 raw[kIt];
-    ld_row_chunks(x, t, H, raw);
+    if (vmask == 0ull) return;      // token selects nothing: no row is produced
+    float scale_out = 0.f;                              // bf16 and MX modes: the meta's scale word is 0
+    u32x4 q[kBf16 ? kChunkItems : kMaxItems];
+    uint32_t sc[kMaxItems];
+    if constexpr (kBf16) ld_row_chunks(x, t, H, q);
+    else if constexpr (kMx) quant_row_mx<QM>(raw, q, sc);
+    else quant_row<QM>(raw, q, scale_out);
     if (LATE) route_token<I32, true>(ll, topk_idx, idx_small, send_off, t, K, E, my_rank, late, e_l, slot_l, dst_l);
-    if (idx_off) {                                  // compact / push staging, see stage_int8_kernel
+    if (idx_off) {
+        // compact staging (normal-mode pull transport): the row is written ONCE at slot t; the expert-sorted index tells the
+        // receivers which token row each of their rows is (K-fold less staging traffic than one copy per (t, k)).
+        // Push transport: the same row + index entries, written into every destination rank's window instead of the own one.
         stage_token_rows(pg, dsts, parity_off(par), idx_off, my_rank, t, K, e_l, slot_l, send_off, [&](uint8_t *base) {
             uint8_t *row = base + (size_t)t * stride;
-            u32x4 *dst = (u32x4 *)row;
-#pragma unroll
-            for (int it = 0; it < kIt; ++it) {
-                const int item = it * kWave + lane;
-                if (item < nitems) dst[item] = raw[it];
-            }
-            if (lane == 0) *(u32x4 *)(row + (size_t)H * 2) = u32x4{0u, (uint32_t)t, 0u, (uint32_t)my_rank};
+            st_quant_row<QM>(StMem<false>{(u32x4 *)row}, row + pl.data, true, H, q, sc, lane);
+            if (lane == 0) *(u32x4 *)(row + pl.meta_off()) = u32x4{__float_as_uint(scale_out), (uint32_t)t, 0u, (uint32_t)my_rank};
         });
         return;
     }
     const size_t poff = parity_off(par);
     for (int k = kpart; k < K; k += ksplit) {
-        if (!((vmask >> k) & 1ull)) continue;
+        if (!((vmask >> k) & 1ull)) continue;          // wave-uniform
         const int slot = __builtin_amdgcn_readlane(slot_l, k);      // k is wave-uniform: v_readlane instead of an LDS round trip
         const int drank = __builtin_amdgcn_readlane(dst_l, k);
         uint8_t *row = (uint8_t *)dsts.p[drank] + poff + (size_t)slot * stride;
-        const u32x4 meta = u32x4{0u, (uint32_t)t, (uint32_t)k, (uint32_t)my_rank};
-        if (LATE) {                                     // written through the caches: see stage_int8_body
-            const __amdgpu_buffer_rsrc_t d = row_rsrc(row, H * 2 + MI_EP_ROW_META_BYTES);
-#pragma unroll
-            for (int it = 0; it < kIt; ++it) {
-                const int item = it * kWave + lane;
-                if (item < nitems) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wt_u32x4, raw[it]), d, item * 16, 0, 17);
-            }
-            u32x4 m = meta;
-            if (late.tag) {
+        u32x4 meta = u32x4{__float_as_uint(scale_out), (uint32_t)t, (uint32_t)k, (uint32_t)my_rank};
+        if constexpr (LATE) {
+            // one-launch low-latency form: the rows are announced to their owners from INSIDE this launch (ll_layout_send_kernel's tail), so
+            // they are written through the caches (sc0 sc1) -- the announcing workgroup then needs no release fence, only every wave's drain
+            const StWT st{row_rsrc(row, pl.meta_off() + MI_EP_ROW_META_BYTES), 0u};
+            st_quant_row<QM>(st, nullptr, false, H, q, sc, lane);
+            if (late.tag) {                                 // tagged rows: the payload is at its owner before the meta word says so
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                m[3] = (uint32_t)my_rank | (late.tag << 8);
+                meta[3] = (uint32_t)my_rank | (late.tag << 8);
             }
-            if (lane == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wt_u32x4, m), d, H * 2, 0, 17);
+            if (lane == 0) st(pl.meta_off() / 16, meta);
             continue;
         }
-        u32x4 *dst = (u32x4 *)row;
-#pragma unroll
-        for (int it = 0; it < kIt; ++it) {
-            const int item = it * kWave + lane;
-            if (item < nitems) dst[item] = raw[it];
-        }
-        if (lane == 0) *(u32x4 *)(row + (size_t)H * 2) = meta;
+        st_quant_row<QM>(StMem<false>{(u32x4 *)row}, row + pl.data, true, H, q, sc, lane);
+        if (lane == 0) *(u32x4 *)(row + pl.meta_off()) = meta;
     }
+}
+
+template <bool I32, int QM>
+__global__ __launch_bounds__(kWave * kStageWaves) void stage_int8_kernel(
+    const uint16_t *__restrict__ x, const void *__restrict__ topk_idx, const int32_t *__restrict__ idx_small,
+    const int32_t *__restrict__ send_off, int T, int K, int H, int E, int my_rank, PeerPtrs dsts, LLGeom ll, int ksplit, size_t idx_off,
+    PushGeom pg, Parity par)
+{
+    stage_body<I32, QM, false>(x, topk_idx, idx_small, send_off, T, K, H, E, my_rank, dsts, ll, ksplit, idx_off, pg, par,
+                               (int)(blockIdx.x * kStageWaves + threadIdx.x / kWave), LateIdx{nullptr, 0, 0u});
 }
 template <bool I32>
 __global__ __launch_bounds__(kWave * kStageWaves) void stage_bf16_kernel(
@@ -510,8 +411,41 @@ __global__ __launch_bounds__(kWave * kStageWaves) void stage_bf16_kernel(
     const int32_t *__restrict__ send_off, int T, int K, int H, int E, int my_rank, PeerPtrs dsts, LLGeom ll, int ksplit, size_t idx_off,
     PushGeom pg, Parity par)
 {
-    stage_bf16_body<I32, false>(x, topk_idx, idx_small, send_off, T, K, H, E, my_rank, dsts, ll, ksplit, idx_off, pg, par,
-                                (int)(blockIdx.x * kStageWaves + threadIdx.x / kWave), LateIdx{nullptr, 0, 0u});
+    stage_body<I32, MI_EP_QUANT_NONE, false>(x, topk_idx, idx_small, send_off, T, K, H, E, my_rank, dsts, ll, ksplit, idx_off, pg, par,
+                                             (int)(blockIdx.x * kStageWaves + threadIdx.x / kWave), LateIdx{nullptr, 0, 0u});
+}
+
+// Inclusive scan of c[0..LW) in LDS by the whole workgroup (c[LW..LW + 16): the wave totals): each thread owns a contiguous chunk,
+// wave scan of the chunk sums, then wave offsets.  Ends behind a barrier.
+__device__ __forceinline__ void lds_incl_scan(int32_t *c, int LW)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int32_t *wave_tot = c + LW;
+    const int per = (LW + blockDim.x - 1) / blockDim.x;
+    const int b0 = min(LW, tid * per), b1 = min(LW, b0 + per);
+    int32_t sum = 0;
+    for (int i = b0; i < b1; ++i) sum += c[i];
+    const int32_t inc = wave_incl_scan_i32(sum);
+    if (lane == 63) wave_tot[wave] = inc;
+    __syncthreads();
+    int32_t run = inc - sum;
+    for (int w = 0; w < wave; ++w) run += wave_tot[w];
+    for (int i = b0; i < b1; ++i) {
+        run += c[i];
+        c[i] = run;
+    }
+    __syncthreads();
+}
+// the tables of a low-latency receive from the scanned counts c: layout_range = c, packed_recv_count per local expert (count_type 0:
+// cumulative, else its own rows)
+__device__ __forceinline__ void write_count_tables(const int32_t *c, int L, int W, int count_type, int32_t *__restrict__ layout_range,
+                                                   int64_t *__restrict__ packed_recv_count)
+{
+    for (int i = threadIdx.x; i < L * W; i += blockDim.x) layout_range[i] = c[i];
+    for (int le = threadIdx.x; le < L; le += blockDim.x) {
+        const int32_t end = c[(le + 1) * W - 1], beg = le ? c[le * W - 1] : 0;
+        packed_recv_count[le] = (count_type == 0) ? (int64_t)end : (int64_t)(end - beg);
+    }
 }
 
 // The count exchange of a low-latency dispatch, run by ONE workgroup (of any size up to 1024 threads): post this rank's per-expert counts
@@ -523,8 +457,7 @@ __device__ __forceinline__ void ll_counts_body(int32_t *c, const PeerPtrs &count
                                                int32_t *__restrict__ layout_range, int64_t *__restrict__ packed_recv_count, int32_t *status,
                                                uint64_t timeout_ticks)
 {
-    const int LW = L * W, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int32_t *wave_tot = c + LW;
+    const int LW = L * W, tid = threadIdx.x;
     // this call's epoch (device-resident counter + 1, or the explicit value) and the ping-pong half of the count granules
     const uint32_t epoch = (uint32_t)ep64;
     const size_t cpoff = (size_t)(ep64 & 1ull) * counts_parity_stride;
@@ -550,26 +483,8 @@ __device__ __forceinline__ void ll_counts_body(int32_t *c, const PeerPtrs &count
         c[i] = (int32_t)(uint32_t)g;
     }
     __syncthreads();
-    // inclusive scan of c[0..LW): each thread owns a contiguous chunk, wave scan of the chunk sums, then wave offsets
-    const int per = (LW + blockDim.x - 1) / blockDim.x;
-    const int b0 = min(LW, tid * per), b1 = min(LW, b0 + per);
-    int32_t sum = 0;
-    for (int i = b0; i < b1; ++i) sum += c[i];
-    const int32_t inc = wave_incl_scan_i32(sum);
-    if (lane == 63) wave_tot[wave] = inc;
-    __syncthreads();
-    int32_t run = inc - sum;
-    for (int w = 0; w < wave; ++w) run += wave_tot[w];
-    for (int i = b0; i < b1; ++i) {
-        run += c[i];
-        c[i] = run;
-    }
-    __syncthreads();
-    for (int i = tid; i < LW; i += blockDim.x) layout_range[i] = c[i];
-    for (int le = tid; le < L; le += blockDim.x) {
-        const int32_t end = c[(le + 1) * W - 1], beg = le ? c[le * W - 1] : 0;
-        packed_recv_count[le] = (count_type == 0) ? (int64_t)end : (int64_t)(end - beg);
-    }
+    lds_incl_scan(c, LW);
+    write_count_tables(c, L, W, count_type, layout_range, packed_recv_count);
     // the call is now "complete" as far as later kernels of the family are concerned: they read the counter with add = 0
     if (epoch_bump && tid == 0) *epoch_bump = ep64;
 }
@@ -637,11 +552,7 @@ __global__ __launch_bounds__(1024) void ll_layout_send_kernel(
         const int wid = (int)(blockIdx.x - 1) * send_waves + wave;
         if (wave < send_waves && wid < npairs) {
             const LateIdx late{smem, wid % K, tail.cur_epoch ? ll_row_tag(*tail.epoch_bump + 1ull) : 0u};
-            if (QM == MI_EP_QUANT_NONE)
-                stage_bf16_body<I32, true>(x, topk_idx, nullptr, nullptr, T, K, H, E, my_rank, dsts, ll, K, (size_t)0, PushGeom{0, 0}, par, wid, late);
-            else
-                stage_int8_body<I32, QM == MI_EP_QUANT_NONE ? MI_EP_QUANT_INT8 : QM, true>(x, topk_idx, nullptr, nullptr, T, K, H, E, my_rank, dsts, ll, K,
-                                                                                            (size_t)0, PushGeom{0, 0}, par, wid, late);
+            stage_body<I32, QM, true>(x, topk_idx, nullptr, nullptr, T, K, H, E, my_rank, dsts, ll, K, (size_t)0, PushGeom{0, 0}, par, wid, late);
         }
         if (!tail.arrive) return;
     }
@@ -727,13 +638,7 @@ __device__ __forceinline__ void pull_body(
     {
 #pragma unroll 1
         for (long long r = (long long)blockIdx.x * kPullWaves + wave; r < total; r += (long long)gridDim.x * kPullWaves) {
-            // first i with cum[i] > r
-            int lo = 0, hi = LW - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (cum[mid] > r) hi = mid; else lo = mid + 1;
-            }
-            const int i = lo;
+            const int i = seg_of(cum, LW, r);
             const int j = (int)(r - (i ? cum[i - 1] : 0));
             const int src = i % W;
             const size_t off = pull_offset ? (size_t)pull_offset[i] : (size_t)i * seg_capacity;
@@ -821,29 +726,9 @@ __global__ __launch_bounds__(kWave * kPullWaves) void ll_wait_pack_kernel(
         c[i] = (int32_t)(uint32_t)g;
     }
     __syncthreads();
-    {   // inclusive scan of c[0..LW) (as ll_counts_body)
-        int32_t *wave_tot = c + LW;
-        const int per = (LW + (int)blockDim.x - 1) / (int)blockDim.x;
-        const int b0 = min(LW, tid * per), b1 = min(LW, b0 + per);
-        int32_t sum = 0;
-        for (int i = b0; i < b1; ++i) sum += c[i];
-        const int32_t inc = wave_incl_scan_i32(sum);
-        if (lane == 63) wave_tot[wave] = inc;
-        __syncthreads();
-        int32_t run = inc - sum;
-        for (int w = 0; w < wave; ++w) run += wave_tot[w];
-        for (int i = b0; i < b1; ++i) {
-            run += c[i];
-            c[i] = run;
-        }
-        __syncthreads();
-    }
+    lds_incl_scan(c, LW);
     if (blockIdx.x == 0) {
-        for (int i = tid; i < LW; i += blockDim.x) layout_range[i] = c[i];
-        for (int le = tid; le < L; le += blockDim.x) {
-            const int32_t end = c[(le + 1) * W - 1], beg = le ? c[le * W - 1] : 0;
-            packed_recv_count[le] = (count_type == 0) ? (int64_t)end : (int64_t)(end - beg);
-        }
+        write_count_tables(c, L, W, count_type, layout_range, packed_recv_count);
         if (tid == 0) *epoch_bump = ep64;
     }
     // rows (pull_body with the tag wait in front of every row)
@@ -852,12 +737,7 @@ __global__ __launch_bounds__(kWave * kPullWaves) void ll_wait_pack_kernel(
     const int n16 = payload_bytes / 16;
 #pragma unroll 1
     for (long long r = (long long)blockIdx.x * kPullWaves + wave; r < total; r += (long long)gridDim.x * kPullWaves) {
-        int lo = 0, hi = LW - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (c[mid] > r) hi = mid; else lo = mid + 1;
-        }
-        const int i = lo;
+        const int i = seg_of(c, LW, r);
         const int j = (int)(r - (i ? c[i - 1] : 0));
         const uint8_t *srow = my_rows + poff + ((size_t)i * seg_capacity + j) * stride;
         if (lane == 0) {
@@ -907,16 +787,12 @@ __global__ __launch_bounds__(kWave * kPullWaves) void pull_indexed_kernel(
     const int n16 = pl.data / 16;
     const long long nw = (long long)gridDim.x * kPullWaves;
     auto entry = [&](long long r, int &src) -> uint2 {          // wave-uniform
-        int lo = 0, hi = LW - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (cum[mid] > r) hi = mid; else lo = mid + 1;
-        }
-        const int j = (int)(r - (lo ? cum[lo - 1] : 0));
-        src = lo % W;
+        const int i = seg_of(cum, LW, r);
+        const int j = (int)(r - (i ? cum[i - 1] : 0));
+        src = i % W;
         if (src == skip_src) return uint2{0u, 0u};                // rows of this rank's own tokens: written by pull_local_kernel
         // a corrupt count / offset must not turn into a wild (possibly cross-GPU) read: the index holds idx_entries entries
-        const size_t pos = min((size_t)max(pull_offset[lo] + j, 0), idx_entries - 1);
+        const size_t pos = min((size_t)max(pull_offset[i] + j, 0), idx_entries - 1);
         return ((const uint2 *)((const uint8_t *)srcs.p[src] + poff + idx_off))[pos];
     };
     long long r = (long long)blockIdx.x * kPullWaves + wave;
@@ -972,16 +848,12 @@ __global__ __launch_bounds__(256) void resolve_rows_kernel(
             row_off[r] = 0;
             continue;
         }
-        int lo = 0, hi = LW - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (cum[mid] > r) hi = mid; else lo = mid + 1;
-        }
-        const int j = (int)(r - (lo ? cum[lo - 1] : 0));
-        const int src = lo % W;
+        const int i = seg_of(cum, LW, r);
+        const int j = (int)(r - (i ? cum[i - 1] : 0));
+        const int src = i % W;
         const uint8_t *sb = (const uint8_t *)srcs.p[src] + poff;
         // a corrupt count / offset / entry must not turn into a wild read: the index holds idx_entries entries, token rows live below it
-        const size_t pos = min((size_t)max(pull_offset[lo] + j, 0), idx_entries - 1);
+        const size_t pos = min((size_t)max(pull_offset[i] + j, 0), idx_entries - 1);
         const uint2 e = ((const uint2 *)(sb + idx_off))[pos];
         const size_t trow = min((size_t)e.x, idx_off / stride - 1);
         const uint8_t *srow = sb + trow * stride;
@@ -1077,7 +949,7 @@ __global__ __launch_bounds__(kWave * kPullWaves) void pull_local_kernel(
 }
 
 // Single-rank dispatch in one pass (mi_ep_dispatch_stage_local): the token row is read from x, quantised in registers by the same
-// code as stage_int8_body (ld_row_items + quant_row; bf16: ld_row_chunks, a plain copy) and stored straight to each of its selections'
+// code as stage_body (ld_row_items + quant_row; bf16: ld_row_chunks, a plain copy) and stored straight to each of its selections'
 // receive rows, with the scale and (0, t, k) triple -- the bytes stage_compact + pull_local_kernel produce at num_ranks == 1, without
 // the staged row in between (T * (H + 16) bytes written, then read back, and one launch).  Output row of selection (t, k):
 // recv_count[e] - num_tokens_per_expert[e] + send_token_idx_small[t, k]; rows below row_capacity only; the write-back / nontemporal
@@ -1113,31 +985,13 @@ __global__ __launch_bounds__(kWave * kStageWaves) void stage_local_kernel(
     uint32_t sc[kMaxItems];
     if constexpr (kMx) quant_row_mx<QM>(raw, q, sc);
     else if constexpr (kQuant) quant_row<QM>(raw, q, scale);
-    const int n16 = kQuant ? H / 16 : H / 8;
     const RowPayload pl = row_payload(H, QM);
     for (unsigned long long m = lmask; m; m &= m - 1) {           // wave-uniform walk over the token's selections
         const int k = __builtin_ctzll(m);
         const int rk = __builtin_amdgcn_readlane(r_l, k);
-        if constexpr (kMx) {
-            uint8_t *row = recv_x + (size_t)rk * pl.data, *sc_row = (uint8_t *)recv_scales + (size_t)rk * pl.scales;
-            if (NT && rk >= nt_from_row) st_quant_row<QM, true>(row, sc_row, (pl.scales & 3) == 0, H, q, sc, lane);
-            else st_quant_row<QM, false>(row, sc_row, (pl.scales & 3) == 0, H, q, sc, lane);
-            continue;
-        }
-        u32x4 *d16 = (u32x4 *)(recv_x + (size_t)rk * pl.data);
-        if (NT && rk >= nt_from_row) {
-#pragma unroll
-            for (int it = 0; it < kIt; ++it) {
-                const int item = it * kWave + lane;
-                if (item < n16) st_row<true>(d16 + item, q[it]);
-            }
-        } else {
-#pragma unroll
-            for (int it = 0; it < kIt; ++it) {
-                const int item = it * kWave + lane;
-                if (item < n16) st_row<false>(d16 + item, q[it]);
-            }
-        }
+        uint8_t *row = recv_x + (size_t)rk * pl.data, *sc_row = (uint8_t *)recv_scales + (size_t)rk * pl.scales;
+        if (NT && rk >= nt_from_row) st_quant_row<QM>(StMem<true>{(u32x4 *)row}, sc_row, (pl.scales & 3) == 0, H, q, sc, lane);
+        else st_quant_row<QM>(StMem<false>{(u32x4 *)row}, sc_row, (pl.scales & 3) == 0, H, q, sc, lane);
     }
     if (r_l >= 0) {                                               // lane k writes the meta of selection k
         if (recv_scales && !kMx) recv_scales[r_l] = scale;
@@ -1152,6 +1006,29 @@ __global__ __launch_bounds__(kWave * kStageWaves) void stage_local_kernel(
 
 using namespace mi_ep;
 
+// Launch-site switches over template parameters: f(std::integral_constant<int, QM>{}) for the runtime quant mode qm, which must lie in
+// [LO, HI] (false, nothing called, otherwise: only the modes in the range are instantiated); f(std::true_type / std::false_type).
+template <int LO, int HI, class F>
+static bool with_quant_mode(int qm, F &&f)
+{
+    if constexpr (LO > HI) {
+        return false;
+    } else {
+        if (qm != LO) return with_quant_mode<LO + 1, HI>(qm, f);
+        f(std::integral_constant<int, LO>{});
+        return true;
+    }
+}
+template <class F>
+static void with_flag(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// pull grid: one row per wave until `cap` workgroups
+static long long pull_blocks(long long rows, long long cap) { return std::min((rows + kPullRowsPerBlock - 1) / kPullRowsPerBlock, cap); }
+
 extern "C" size_t mi_ep_dispatch_row_bytes(int hidden, int quant_mode)
 {
     return row_payload(hidden, quant_mode).stride();
@@ -1164,6 +1041,31 @@ extern "C" size_t mi_ep_dispatch_index_offset(int hidden, int quant_mode, int to
     return cap * rb;
 }
 
+// the stage kernel of quant mode QM; bf16 rows keep an entry point of their own (profiles look kernels up by name)
+template <bool I32, int QM>
+static constexpr auto stage_kernel()
+{
+    if constexpr (QM == MI_EP_QUANT_NONE) return stage_bf16_kernel<I32>;
+    else return stage_int8_kernel<I32, QM>;
+}
+
+// one stage launch, normal (ll.L == 0) or low-latency geometry, for the quant modes up to QM_HI
+template <int QM_HI>
+static int stage_kernels(const void *x, const void *topk_idx, bool i32, const int32_t *send_token_idx_small, const int32_t *send_data_offset,
+                         int T, int K, int H, int E, int my_rank, int quant_mode, const PeerPtrs &pp, LLGeom ll, size_t idx_off, PushGeom pg,
+                         Parity par, void *stream)
+{
+    const int ksplit = (T <= 512 && !idx_off) ? K : 1;   // decode-size batches: one wave per (token, k) instead of per token
+    const int blocks = (int)(((long long)T * ksplit + kStageWaves - 1) / kStageWaves);
+    const bool ok = with_quant_mode<MI_EP_QUANT_NONE, QM_HI>(quant_mode, [&](auto qm) {
+        with_flag(i32, [&](auto i32c) {
+            stage_kernel<i32c, qm>()<<<blocks, kWave * kStageWaves, 0, (hipStream_t)stream>>>(
+                (const uint16_t *)x, topk_idx, send_token_idx_small, send_data_offset, T, K, H, E, my_rank, pp, ll, ksplit, idx_off, pg, par);
+        });
+    });
+    return ok ? launch_status() : MI_EP_EINVAL;
+}
+
 static int stage_launch(const void *x, const void *topk_idx, int idx_is_i32, const int32_t *send_token_idx_small,
                         const int32_t *send_data_offset, int T, int K, int H, int E, int my_rank, int quant_mode, void *rows,
                         size_t idx_off, void *stream, const PeerPtrs *push_peers = nullptr, PushGeom pg = PushGeom{0, 0},
@@ -1172,45 +1074,11 @@ static int stage_launch(const void *x, const void *topk_idx, int idx_is_i32, con
     if (T < 0 || K <= 0 || K > MI_EP_MAX_TOPK || !dispatch_mode_ok(quant_mode, H) || H > MI_EP_MAX_HIDDEN || E <= 0) return MI_EP_EINVAL;
     if (T == 0) return MI_EP_OK;
     if (!x || !topk_idx || !send_token_idx_small || !send_data_offset || (!rows && !push_peers)) return MI_EP_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const int ksplit = (T <= 512 && !idx_off) ? K : 1;   // decode-size batches: one wave per (token, k) instead of per token
-    const int blocks = (int)(((long long)T * ksplit + kStageWaves - 1) / kStageWaves);
-    const int threads = kWave * kStageWaves;
-    const uint16_t *xp = (const uint16_t *)x;
-    uint8_t *rp = (uint8_t *)rows;
     PeerPtrs pp;
     if (push_peers) pp = *push_peers;
-    else pp.p[0] = rp;
-    const LLGeom ll{0, 0, 0};
-#define MI_EP_STAGE(KERNEL) \
-    KERNEL<<<blocks, threads, 0, s>>>(xp, topk_idx, send_token_idx_small, send_data_offset, T, K, H, E, my_rank, pp, ll, ksplit, idx_off, pg, par)
-    switch (quant_mode) {
-        case MI_EP_QUANT_NONE:
-            if (idx_is_i32) MI_EP_STAGE(stage_bf16_kernel<true>); else MI_EP_STAGE(stage_bf16_kernel<false>);
-            break;
-        case MI_EP_QUANT_INT8:
-            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_INT8>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_INT8>));
-            break;
-        case MI_EP_QUANT_INT8_NOEPS:
-            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_INT8_NOEPS>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_INT8_NOEPS>));
-            break;
-        case MI_EP_QUANT_FP8_E4M3:
-            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_FP8_E4M3>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_FP8_E4M3>));
-            break;
-        case MI_EP_QUANT_MXFP8_E4M3:
-            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_MXFP8_E4M3>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_MXFP8_E4M3>));
-            break;
-        case MI_EP_QUANT_MXFP8_E5M2:
-            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_MXFP8_E5M2>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_MXFP8_E5M2>));
-            break;
-        case MI_EP_QUANT_MXFP4_E2M1:
-            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_MXFP4_E2M1>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_MXFP4_E2M1>));
-            break;
-        default:
-            return MI_EP_EINVAL;
-    }
-#undef MI_EP_STAGE
-    return launch_status();
+    else pp.p[0] = rows;
+    return stage_kernels<MI_EP_QUANT_MXFP4_E2M1>(x, topk_idx, idx_is_i32, send_token_idx_small, send_data_offset, T, K, H, E, my_rank, quant_mode,
+                                                 pp, LLGeom{0, 0, 0}, idx_off, pg, par, stream);
 }
 
 extern "C" int mi_ep_dispatch_stage(const void *x, const void *topk_idx, int idx_is_i32,
@@ -1252,10 +1120,7 @@ extern "C" int mi_ep_dispatch_stage_push(const void *x, const void *topk_idx, in
     const size_t idx_off = mi_ep_dispatch_index_offset(H, quant_mode, K, slab);
     if (idx_off == 0 || (size_t)T > idx_off / rb) return MI_EP_EINVAL;          // a slab cannot hold T tokens
     PeerPtrs pp;
-    for (int i = 0; i < W; ++i) {
-        if (!peer_region_host[i]) return MI_EP_EINVAL;
-        pp.p[i] = peer_region_host[i];
-    }
+    if (!peer_ptrs(peer_region_host, W, pp)) return MI_EP_EINVAL;
     return stage_launch(x, topk_idx, idx_is_i32, send_token_idx_small, send_data_offset, T, K, H, E, my_rank, quant_mode, nullptr,
                         idx_off, stream, &pp, PushGeom{E / W, slab}, make_parity(epoch_ctr, 1, parity_stride));
 }
@@ -1269,15 +1134,10 @@ extern "C" int mi_ep_dispatch_pull(const void *const *src_base_host, const int32
         return MI_EP_EINVAL;
     if (rows_hint <= 0) return MI_EP_OK;
     PeerPtrs pp;
-    for (int i = 0; i < W; ++i) {
-        if (!src_base_host[i]) return MI_EP_EINVAL;
-        pp.p[i] = const_cast<void *>(src_base_host[i]);
-    }
+    if (!peer_ptrs(src_base_host, W, pp)) return MI_EP_EINVAL;
     const RowPayload pl = row_payload(H, quant_mode);
-    long long blocks = ((long long)rows_hint + kPullRowsPerBlock - 1) / kPullRowsPerBlock;
-    if (blocks > 256 * 8) blocks = 256 * 8;
     const size_t lds = (size_t)L * W * sizeof(int32_t);
-    pull_kernel<<<(int)blocks, kWave * kPullWaves, lds, (hipStream_t)stream>>>(
+    pull_kernel<<<(int)pull_blocks(rows_hint, 256 * 8), kWave * kPullWaves, lds, (hipStream_t)stream>>>(
         pp, recv_count, pull_offset, 0, W, L * W, pl, (uint8_t *)recv_x, recv_x_scales, recv_src_idx, rows_hint,
         Parity{EpochRef{nullptr, 0}, 0});
     return launch_status();
@@ -1294,25 +1154,19 @@ extern "C" int mi_ep_dispatch_pull_indexed(const void *const *src_base_host, con
         return MI_EP_EINVAL;
     if (rows_hint <= 0) return MI_EP_OK;
     PeerPtrs pp;
-    for (int i = 0; i < W; ++i) {
-        if (!src_base_host[i]) return MI_EP_EINVAL;
-        pp.p[i] = const_cast<void *>(src_base_host[i]);
-    }
+    if (!peer_ptrs(src_base_host, W, pp)) return MI_EP_EINVAL;
     const size_t idx_off = mi_ep_dispatch_index_offset(H, quant_mode, K, region_bytes);
     if (idx_off == 0) return MI_EP_EINVAL;
     const RowPayload pl = row_payload(H, quant_mode);
-    long long blocks = ((long long)rows_hint + kPullRowsPerBlock - 1) / kPullRowsPerBlock;
     static const long long cap = getenv("MI_EP_PULL_BLOCKS") ? atoll(getenv("MI_EP_PULL_BLOCKS")) : 256 * 8;
-    if (blocks > cap) blocks = cap;
+    const long long blocks = pull_blocks(rows_hint, cap);
     const size_t lds = (size_t)L * W * sizeof(int32_t);
-#define MI_EP_PULL_INDEXED(NT)                                                                                                      \
-    pull_indexed_kernel<NT><<<(int)blocks, kWave * kPullWaves, lds, (hipStream_t)stream>>>(                                         \
-        pp, recv_count, pull_offset, W, L * W, pl, idx_off, (idx_off / mi_ep_dispatch_row_bytes(H, quant_mode)) * (size_t)K,  \
-        (uint8_t *)recv_x, recv_x_scales, recv_src_idx, rows_hint, make_parity(epoch_ctr, 0, parity_stride), skip_src < 0 ? -1 : skip_src, \
-        nt_from)
     const int nt_from = pull_nt_from_row(rows_hint, pl.data + pl.scales);
-    if (nt_from != 0x7fffffff) MI_EP_PULL_INDEXED(true); else MI_EP_PULL_INDEXED(false);
-#undef MI_EP_PULL_INDEXED
+    with_flag(nt_from != 0x7fffffff, [&](auto nt) {
+        pull_indexed_kernel<nt><<<(int)blocks, kWave * kPullWaves, lds, (hipStream_t)stream>>>(
+            pp, recv_count, pull_offset, W, L * W, pl, idx_off, (idx_off / mi_ep_dispatch_row_bytes(H, quant_mode)) * (size_t)K, (uint8_t *)recv_x,
+            recv_x_scales, recv_src_idx, rows_hint, make_parity(epoch_ctr, 0, parity_stride), skip_src < 0 ? -1 : skip_src, nt_from);
+    });
     return launch_status();
 }
 
@@ -1327,14 +1181,9 @@ extern "C" int mi_ep_dispatch_resolve_rows(const void *const *src_base_host, con
     const size_t idx_off = mi_ep_dispatch_index_offset(H, quant_mode, K, region_bytes);
     if (idx_off == 0) return MI_EP_EINVAL;
     PeerPtrs pp;
-    const uint8_t *lo = nullptr, *hi = nullptr;
-    for (int i = 0; i < W; ++i) {
-        if (!src_base_host[i]) return MI_EP_EINVAL;
-        pp.p[i] = const_cast<void *>(src_base_host[i]);
-        const uint8_t *b = (const uint8_t *)src_base_host[i];
-        if (!lo || b < lo) lo = b;
-        if (!hi || b > hi) hi = b;
-    }
+    if (!peer_ptrs(src_base_host, W, pp)) return MI_EP_EINVAL;
+    const auto [lo_p, hi_p] = std::minmax_element((uint8_t *const *)pp.p, (uint8_t *const *)pp.p + W);
+    const uint8_t *lo = *lo_p, *hi = *hi_p;
     // every staged row (either ping-pong half) must lie within 32 bits of the lowest base
     if ((size_t)(hi - lo) + (epoch_ctr ? parity_stride : 0) + idx_off > 0xFFFFFFFFull) return MI_EP_ESIZE;
     *a_base_out = lo;
@@ -1363,16 +1212,13 @@ extern "C" int mi_ep_dispatch_pull_local(const void *my_rows, const void *topk_i
     const int blocks = (T + kPullWaves - 1) / kPullWaves;
     const Parity par = make_parity(epoch_ctr, 0, parity_stride);
     const int nt_from = pull_nt_from_row(rows_hint, pl.data + pl.scales);
-    const bool nt = nt_from != 0x7fffffff;
-#define MI_EP_PULL_LOCAL(I32)                                                                                                       \
-    if (nt) MI_EP_PULL_LOCAL2(I32, true); else MI_EP_PULL_LOCAL2(I32, false)
-#define MI_EP_PULL_LOCAL2(I32, NT)                                                                                                  \
-    pull_local_kernel<I32, NT><<<blocks, kWave * kPullWaves, 0, (hipStream_t)stream>>>(                                                \
-        (const uint8_t *)my_rows, topk_idx, send_token_idx_small, recv_count, num_tokens_per_expert, T, K, E, W, my_rank, pl, \
-        (uint8_t *)recv_x, recv_x_scales, recv_src_idx, rows_hint, par, nt_from, local_row_out)
-    if (idx_is_i32) { MI_EP_PULL_LOCAL(true); } else { MI_EP_PULL_LOCAL(false); }
-#undef MI_EP_PULL_LOCAL
-#undef MI_EP_PULL_LOCAL2
+    with_flag(idx_is_i32, [&](auto i32) {
+        with_flag(nt_from != 0x7fffffff, [&](auto nt) {
+            pull_local_kernel<i32, nt><<<blocks, kWave * kPullWaves, 0, (hipStream_t)stream>>>(
+                (const uint8_t *)my_rows, topk_idx, send_token_idx_small, recv_count, num_tokens_per_expert, T, K, E, W, my_rank, pl,
+                (uint8_t *)recv_x, recv_x_scales, recv_src_idx, rows_hint, par, nt_from, local_row_out);
+        });
+    });
     return launch_status();
 }
 
@@ -1390,27 +1236,15 @@ extern "C" int mi_ep_dispatch_stage_local(const void *x, const void *topk_idx, i
     const RowPayload pl = row_payload(H, quant_mode);
     const int blocks = (T + kStageWaves - 1) / kStageWaves;
     const int nt_from = pull_nt_from_row(rows_hint, pl.data + pl.scales);
-    const bool nt = nt_from != 0x7fffffff;
-#define MI_EP_STAGE_LOCAL3(I32, QM, NT)                                                                                             \
-    stage_local_kernel<I32, QM, NT><<<blocks, kWave * kStageWaves, 0, (hipStream_t)stream>>>(                                          \
-        (const uint16_t *)x, topk_idx, send_token_idx_small, recv_count, num_tokens_per_expert, T, K, H, E, (uint8_t *)recv_x,       \
-        recv_x_scales, recv_src_idx, rows_hint, nt_from, local_row_out)
-#define MI_EP_STAGE_LOCAL2(I32, QM)                                                                                                 \
-    if (nt) MI_EP_STAGE_LOCAL3(I32, QM, true); else MI_EP_STAGE_LOCAL3(I32, QM, false)
-#define MI_EP_STAGE_LOCAL(QM)                                                                                                       \
-    if (idx_is_i32) { MI_EP_STAGE_LOCAL2(true, QM); } else { MI_EP_STAGE_LOCAL2(false, QM); }
-    switch (quant_mode) {
-        case MI_EP_QUANT_NONE: MI_EP_STAGE_LOCAL(MI_EP_QUANT_NONE); break;
-        case MI_EP_QUANT_INT8: MI_EP_STAGE_LOCAL(MI_EP_QUANT_INT8); break;
-        case MI_EP_QUANT_INT8_NOEPS: MI_EP_STAGE_LOCAL(MI_EP_QUANT_INT8_NOEPS); break;
-        case MI_EP_QUANT_FP8_E4M3: MI_EP_STAGE_LOCAL(MI_EP_QUANT_FP8_E4M3); break;
-        case MI_EP_QUANT_MXFP8_E4M3: MI_EP_STAGE_LOCAL(MI_EP_QUANT_MXFP8_E4M3); break;
-        case MI_EP_QUANT_MXFP8_E5M2: MI_EP_STAGE_LOCAL(MI_EP_QUANT_MXFP8_E5M2); break;
-        default: MI_EP_STAGE_LOCAL(MI_EP_QUANT_MXFP4_E2M1); break;
-    }
-#undef MI_EP_STAGE_LOCAL
-#undef MI_EP_STAGE_LOCAL2
-#undef MI_EP_STAGE_LOCAL3
+    with_quant_mode<MI_EP_QUANT_NONE, MI_EP_QUANT_MXFP4_E2M1>(quant_mode, [&](auto qm) {
+        with_flag(idx_is_i32, [&](auto i32) {
+            with_flag(nt_from != 0x7fffffff, [&](auto nt) {
+                stage_local_kernel<i32, qm, nt><<<blocks, kWave * kStageWaves, 0, (hipStream_t)stream>>>(
+                    (const uint16_t *)x, topk_idx, send_token_idx_small, recv_count, num_tokens_per_expert, T, K, H, E, (uint8_t *)recv_x,
+                    recv_x_scales, recv_src_idx, rows_hint, nt_from, local_row_out);
+            });
+        });
+    });
     return launch_status();
 }
 
@@ -1454,37 +1288,9 @@ extern "C" int mi_ep_ll_dispatch_send(const void *x, const void *topk_idx, int i
     if (T == 0) return MI_EP_OK;
     if (!x || !topk_idx || !send_token_idx_small) return MI_EP_EINVAL;
     PeerPtrs pp;
-    for (int i = 0; i < W; ++i) {
-        if (!peer_rows_host[i]) return MI_EP_EINVAL;
-        pp.p[i] = peer_rows_host[i];
-    }
-    const LLGeom ll{E / W, W, max_tokens};
-    const Parity par = make_parity(epoch_ctr, 1, parity_stride);
-    hipStream_t s = (hipStream_t)stream;
-    const int ksplit = T <= 512 ? K : 1;            // decode-size batches: one wave per (token, k) instead of per token
-    const int blocks = (int)(((long long)T * ksplit + kStageWaves - 1) / kStageWaves);
-    const int threads = kWave * kStageWaves;
-    const uint16_t *xp = (const uint16_t *)x;
-#define MI_EP_STAGE(KERNEL) \
-    KERNEL<<<blocks, threads, 0, s>>>(xp, topk_idx, send_token_idx_small, nullptr, T, K, H, E, my_rank, pp, ll, ksplit, (size_t)0, PushGeom{0, 0}, par)
-    switch (quant_mode) {
-        case MI_EP_QUANT_NONE:
-            if (idx_is_i32) MI_EP_STAGE(stage_bf16_kernel<true>); else MI_EP_STAGE(stage_bf16_kernel<false>);
-            break;
-        case MI_EP_QUANT_INT8:
-            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_INT8>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_INT8>));
-            break;
-        case MI_EP_QUANT_INT8_NOEPS:
-            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_INT8_NOEPS>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_INT8_NOEPS>));
-            break;
-        case MI_EP_QUANT_FP8_E4M3:
-            if (idx_is_i32) MI_EP_STAGE((stage_int8_kernel<true, MI_EP_QUANT_FP8_E4M3>)); else MI_EP_STAGE((stage_int8_kernel<false, MI_EP_QUANT_FP8_E4M3>));
-            break;
-        default:
-            return MI_EP_EINVAL;
-    }
-#undef MI_EP_STAGE
-    return launch_status();
+    if (!peer_ptrs(peer_rows_host, W, pp)) return MI_EP_EINVAL;
+    return stage_kernels<MI_EP_QUANT_FP8_E4M3>(x, topk_idx, idx_is_i32, send_token_idx_small, nullptr, T, K, H, E, my_rank, quant_mode, pp,
+                                               LLGeom{E / W, W, max_tokens}, 0, PushGeom{0, 0}, make_parity(epoch_ctr, 1, parity_stride), stream);
 }
 
 static int ll_layout_send_launch(const void *x, const void *topk_idx, int idx_is_i32, int T, int K, int H, int E, int W, int my_rank,
@@ -1502,10 +1308,7 @@ static int ll_layout_send_launch(const void *x, const void *topk_idx, int idx_is
     if ((T + ut - 1) / ut > 16 || (size_t)16 * E > 16384 || ((16 * E) & 1)) return MI_EP_EINVAL;
     if (T > 0 && (!x || !topk_idx || !is_token_in_rank || !send_token_idx_small)) return MI_EP_EINVAL;
     PeerPtrs pp;
-    for (int i = 0; i < W; ++i) {
-        if (!peer_rows_host[i]) return MI_EP_EINVAL;
-        pp.p[i] = peer_rows_host[i];
-    }
+    if (!peer_ptrs(peer_rows_host, W, pp)) return MI_EP_EINVAL;
     const LLGeom ll{E / W, W, max_tokens};
     const Parity par = make_parity(epoch_ctr, 1, parity_stride);
     hipStream_t s = (hipStream_t)stream;
@@ -1519,33 +1322,24 @@ static int ll_layout_send_launch(const void *x, const void *topk_idx, int idx_is
     // dynamic LDS: the layout workgroup's tables, the send workgroups' copy of the routing table (int32 per pair), the tail's counts
     const size_t lds = std::max(std::max(layout_small_lds_bytes(E, W, ut), (size_t)T * K * sizeof(int32_t)), tail_in ? (size_t)(E + 16) * 4 : (size_t)0);
     const uint16_t *xp = (const uint16_t *)x;
+    // the kernel of quant mode qm (low-latency: modes 0-3), index width and layout unit (16 or kLayoutUnitTokens tokens)
+    auto with_kernel = [](int qm, bool i32, bool ut16, auto f) {
+        return with_quant_mode<MI_EP_QUANT_NONE, MI_EP_QUANT_FP8_E4M3>(qm, [&](auto q) {
+            with_flag(i32, [&](auto i) { with_flag(ut16, [&](auto u) { f(ll_layout_send_kernel<i, q, u ? 16 : kLayoutUnitTokens>); }); });
+        });
+    };
     static PerDeviceOnce attr_once;
-#define MI_EP_LLS_ATTR(I32, QM, UT) (void)hipFuncSetAttribute((const void *)ll_layout_send_kernel<I32, QM, UT>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)
-    if (attr_once.need()) {
-        MI_EP_LLS_ATTR(true, MI_EP_QUANT_NONE, 16); MI_EP_LLS_ATTR(false, MI_EP_QUANT_NONE, 16); MI_EP_LLS_ATTR(true, MI_EP_QUANT_NONE, 64); MI_EP_LLS_ATTR(false, MI_EP_QUANT_NONE, 64);
-        MI_EP_LLS_ATTR(true, MI_EP_QUANT_INT8, 16); MI_EP_LLS_ATTR(false, MI_EP_QUANT_INT8, 16); MI_EP_LLS_ATTR(true, MI_EP_QUANT_INT8, 64); MI_EP_LLS_ATTR(false, MI_EP_QUANT_INT8, 64);
-        MI_EP_LLS_ATTR(true, MI_EP_QUANT_INT8_NOEPS, 16); MI_EP_LLS_ATTR(false, MI_EP_QUANT_INT8_NOEPS, 16); MI_EP_LLS_ATTR(true, MI_EP_QUANT_INT8_NOEPS, 64); MI_EP_LLS_ATTR(false, MI_EP_QUANT_INT8_NOEPS, 64);
-        MI_EP_LLS_ATTR(true, MI_EP_QUANT_FP8_E4M3, 16); MI_EP_LLS_ATTR(false, MI_EP_QUANT_FP8_E4M3, 16); MI_EP_LLS_ATTR(true, MI_EP_QUANT_FP8_E4M3, 64); MI_EP_LLS_ATTR(false, MI_EP_QUANT_FP8_E4M3, 64);
-    }
-#undef MI_EP_LLS_ATTR
-#define MI_EP_LLS(I32, QM, UT)                                                                                                         \
-    ll_layout_send_kernel<I32, QM, UT><<<blocks, 1024, lds, s>>>(xp, topk_idx, T, K, H, E, W, nbits, my_rank, pp, ll, par,              \
-                                                                  num_tokens_per_rank, num_tokens_per_expert, is_token_in_rank,         \
-                                                                  send_token_idx_small, send_data_offset, send_waves, tail)
-#define MI_EP_LLS_Q(QM)                                                                                       \
-    do {                                                                                                      \
-        if (ut == 16) { if (idx_is_i32) MI_EP_LLS(true, QM, 16); else MI_EP_LLS(false, QM, 16); }             \
-        else { if (idx_is_i32) MI_EP_LLS(true, QM, 64); else MI_EP_LLS(false, QM, 64); }                      \
-    } while (0)
-    switch (quant_mode) {
-        case MI_EP_QUANT_NONE: MI_EP_LLS_Q(MI_EP_QUANT_NONE); break;
-        case MI_EP_QUANT_INT8: MI_EP_LLS_Q(MI_EP_QUANT_INT8); break;
-        case MI_EP_QUANT_INT8_NOEPS: MI_EP_LLS_Q(MI_EP_QUANT_INT8_NOEPS); break;
-        case MI_EP_QUANT_FP8_E4M3: MI_EP_LLS_Q(MI_EP_QUANT_FP8_E4M3); break;
-        default: return MI_EP_EINVAL;
-    }
-#undef MI_EP_LLS_Q
-#undef MI_EP_LLS
+    if (attr_once.need())
+        for (int qm = MI_EP_QUANT_NONE; qm <= MI_EP_QUANT_FP8_E4M3; ++qm)
+            for (int v = 0; v < 4; ++v)
+                with_kernel(qm, v & 1, v & 2, [](auto k) {
+                    (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+                });
+    if (!with_kernel(quant_mode, idx_is_i32, ut == 16, [&](auto k) {
+            k<<<blocks, 1024, lds, s>>>(xp, topk_idx, T, K, H, E, W, nbits, my_rank, pp, ll, par, num_tokens_per_rank, num_tokens_per_expert,
+                                        is_token_in_rank, send_token_idx_small, send_data_offset, send_waves, tail);
+        }))
+        return MI_EP_EINVAL;
     return launch_status();
 }
 
@@ -1577,10 +1371,7 @@ extern "C" int mi_ep_ll_dispatch_layout_send_counts(const void *x, const void *t
     tail.arrive = arrive_word, tail.granules_base = my_counts, tail.counts_parity_stride = counts_parity_stride, tail.epoch_bump = epoch_ctr;
     tail.L = E / W, tail.count_type = count_type, tail.layout_range = layout_range, tail.packed_recv_count = packed_recv_count;
     tail.status = status, tail.timeout_ticks = (uint64_t)(timeout_ms > 0 ? timeout_ms : 10000) * 100000ull;
-    for (int i = 0; i < W; ++i) {
-        if (!peer_counts_host[i]) return MI_EP_EINVAL;
-        tail.count_peers.p[i] = peer_counts_host[i];
-    }
+    if (!peer_ptrs(peer_counts_host, W, tail.count_peers)) return MI_EP_EINVAL;
     return ll_layout_send_launch(x, topk_idx, idx_is_i32, T, K, H, E, W, my_rank, max_tokens, quant_mode, peer_rows_host, epoch_ctr, parity_stride,
                                  num_tokens_per_rank, num_tokens_per_expert, is_token_in_rank, send_token_idx_small, send_data_offset, &tail,
                                  stream);
@@ -1597,10 +1388,7 @@ extern "C" int mi_ep_ll_dispatch_layout_send_tagged(const void *x, const void *t
     if (!epoch_ctr || !peer_counts_host || !cur_epoch_word || W <= 0 || W > MI_EP_MAX_RANKS || E <= 0 || E % W || E > 2048) return MI_EP_EINVAL;
     LLTail tail{};
     tail.counts_parity_stride = counts_parity_stride, tail.epoch_bump = const_cast<uint64_t *>(epoch_ctr), tail.L = E / W, tail.cur_epoch = cur_epoch_word;
-    for (int i = 0; i < W; ++i) {
-        if (!peer_counts_host[i]) return MI_EP_EINVAL;
-        tail.count_peers.p[i] = peer_counts_host[i];
-    }
+    if (!peer_ptrs(peer_counts_host, W, tail.count_peers)) return MI_EP_EINVAL;
     return ll_layout_send_launch(x, topk_idx, idx_is_i32, T, K, H, E, W, my_rank, max_tokens, quant_mode, peer_rows_host, epoch_ctr, parity_stride,
                                  num_tokens_per_rank, num_tokens_per_expert, is_token_in_rank, send_token_idx_small, send_data_offset, &tail,
                                  stream);
@@ -1619,13 +1407,12 @@ extern "C" int mi_ep_ll_wait_pack(const void *my_rows, const uint64_t *my_counts
     const int cap = rows_capacity > 0 ? rows_capacity : L * W * max_tokens;
     const RowPayload pl = row_payload(H, quant_mode);
     // the waves of this launch WAIT for rows: at most 512 workgroups (a quarter of the chip's slots), the rows are grid-strided
-    long long blocks = ((long long)L * W * max_tokens + kPullRowsPerBlock - 1) / kPullRowsPerBlock;
     // MI_EP_LL_WAIT_BLOCKS (measurement / shared-GPU setups): with two PROCESSES on one GPU, 512 waiting workgroups of one (two on every CU) keep
     // the other's 1024-thread send workgroups from starting -- (2 ranks, 300 tokens, H = 2048) timed out in half of the runs and took 9-30 s in
     // the others; capped at 64 the same case runs in 2 s every time, and a longer sleep between polls changes nothing (it is placement, not
     // polling traffic).  Ranks that share a GPU therefore default to the three-launch form (deep_ep.hpp); one rank per GPU has no such peer.
     static const long long cap_env = getenv("MI_EP_LL_WAIT_BLOCKS") ? atoll(getenv("MI_EP_LL_WAIT_BLOCKS")) : 512;
-    if (blocks > cap_env) blocks = cap_env;
+    long long blocks = pull_blocks((long long)L * W * max_tokens, cap_env);
     if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;      // (the caller knows that ranks share this GPU)
     if (blocks < 1) blocks = 1;
     ll_wait_pack_kernel<<<(int)blocks, kWave * kPullWaves, (size_t)(L * W + 16) * 4, (hipStream_t)stream>>>(
@@ -1649,9 +1436,7 @@ extern "C" int mi_ep_ll_pack(const void *my_rows, const int32_t *layout_range, i
     for (int i = 0; i < W; ++i) pp.p[i] = const_cast<void *>(my_rows);
     const int cap = rows_capacity > 0 ? rows_capacity : L * W * max_tokens;      // rows the caller's output buffers hold
     const RowPayload pl = row_payload(H, quant_mode);
-    long long blocks = ((long long)L * W * max_tokens + kPullRowsPerBlock - 1) / kPullRowsPerBlock;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    if (blocks < 1) blocks = 1;
+    const long long blocks = std::max(pull_blocks((long long)L * W * max_tokens, 256 * 8), 1ll);
     pull_kernel<<<(int)blocks, kWave * kPullWaves, (size_t)L * W * 4, (hipStream_t)stream>>>(pp, layout_range, nullptr, max_tokens, W, L * W, pl,
                                                                                          (uint8_t *)packed_recv_x, packed_recv_x_scales, src_info,
                                                                                          cap, make_parity(epoch_ctr, 0, rows_parity_stride));
@@ -1664,10 +1449,7 @@ extern "C" int mi_ep_ll_post_counts(uint64_t *const *peer_counts_host, const int
     if (!peer_counts_host || !num_tokens_per_expert || E <= 0 || W <= 0 || W > MI_EP_MAX_RANKS || E % W || epoch == 0)
         return MI_EP_EINVAL;
     PeerPtrs pp;
-    for (int i = 0; i < W; ++i) {
-        if (!peer_counts_host[i]) return MI_EP_EINVAL;
-        pp.p[i] = peer_counts_host[i];
-    }
+    if (!peer_ptrs(peer_counts_host, W, pp)) return MI_EP_EINVAL;
     ll_post_counts_kernel<<<W, 64, 0, (hipStream_t)stream>>>(pp, num_tokens_per_expert, E / W, W, my_rank, epoch);
     return launch_status();
 }
@@ -1694,9 +1476,7 @@ extern "C" int mi_ep_ll_dispatch_recv(const void *my_rows, const uint64_t *my_co
     // 16-row block, capped: the kernel grid-strides over the device-side total.
     // worst case rows = every (local expert, source) slab full; the kernel grid-strides over the device-side total, so
     // size the grid to fill the chip even for decode-size batches (a 128-token call has ~1 K rows = 7 MB to move)
-    long long blocks = ((long long)L * W * max_tokens + kPullRowsPerBlock - 1) / kPullRowsPerBlock;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    if (blocks < 1) blocks = 1;
+    const long long blocks = std::max(pull_blocks((long long)L * W * max_tokens, 256 * 8), 1ll);
     pull_kernel<<<(int)blocks, kWave * kPullWaves, (size_t)L * W * 4, s>>>(pp, layout_range, nullptr, max_tokens, W, L * W,
                                                                          pl, (uint8_t *)packed_recv_x,
                                                                          packed_recv_x_scales, src_info, cap,
@@ -1717,11 +1497,8 @@ extern "C" int mi_ep_ll_post_recv(uint64_t *const *peer_counts_host, const int32
         H % 16 || max_tokens <= 0 || (epoch == 0 && !epoch_ctr))
         return MI_EP_EINVAL;
     PeerPtrs cp, pp;
-    for (int i = 0; i < W; ++i) {
-        if (!peer_counts_host[i]) return MI_EP_EINVAL;
-        cp.p[i] = peer_counts_host[i];
-        pp.p[i] = const_cast<void *>(my_rows);
-    }
+    if (!peer_ptrs(peer_counts_host, W, cp)) return MI_EP_EINVAL;
+    for (int i = 0; i < W; ++i) pp.p[i] = const_cast<void *>(my_rows);
     hipStream_t s = (hipStream_t)stream;
     const uint64_t ticks = (uint64_t)(timeout_ms > 0 ? timeout_ms : 10000) * 100000ull;
     // only ONE workgroup ever spins on the peers (a chip full of spinning workgroups would starve whatever else has to run
@@ -1732,9 +1509,7 @@ extern "C" int mi_ep_ll_post_recv(uint64_t *const *peer_counts_host, const int32
                                                             layout_range, packed_recv_count, status, ticks);
     const int cap = rows_capacity > 0 ? rows_capacity : L * W * max_tokens;      // rows the caller's output buffers hold
     const RowPayload pl = row_payload(H, quant_mode);
-    long long blocks = ((long long)L * W * max_tokens + kPullRowsPerBlock - 1) / kPullRowsPerBlock;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    if (blocks < 1) blocks = 1;
+    const long long blocks = std::max(pull_blocks((long long)L * W * max_tokens, 256 * 8), 1ll);
     pull_kernel<<<(int)blocks, kWave * kPullWaves, (size_t)L * W * 4, s>>>(pp, layout_range, nullptr, max_tokens, W, L * W, pl,
                                                                          (uint8_t *)packed_recv_x, packed_recv_x_scales, src_info, cap,
                                                                          make_parity(epoch_ctr, 0, rows_parity_stride));

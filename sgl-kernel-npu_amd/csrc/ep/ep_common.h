@@ -88,146 +88,128 @@ __device__ __forceinline__ float wave_max(float v)
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 
-// ---- row copy by one wave.  N pieces of 1 KB (lane l moves 16 B at s[64 u], u < N): all loads back to back, then all stores, in
-// straight-line code.  Written as `for u < 8: if (item < n16) v[u] = load(...)` the compiler gave every load and every store its own
-// block with an s_waitcnt vmcnt(0) in front of it: sixteen serial round trips per 8 KB, each store waiting for the (possibly remote)
-// acknowledgement of the one before (combine_push, pull_indexed and the low-latency pull were all compiled that way).
-// NTL / NTS: nontemporal loads / stores.
-template <int N, bool NTL, bool NTS>
-__device__ __forceinline__ void copy_pieces(const u32x4 *s, u32x4 *d)
-{
-    u32x4 v[N];
-#pragma unroll
-    for (int u = 0; u < N; ++u) v[u] = NTL ? __builtin_nontemporal_load(s + u * kWave) : s[u * kWave];
-#pragma unroll
-    for (int u = 0; u < N; ++u) {
-        if (NTS) __builtin_nontemporal_store(v[u], d + u * kWave);
-        else d[u * kWave] = v[u];
-    }
-}
-// a row of n16 16-byte items: whole pieces in groups of up to eight (the group size is wave-uniform), then the items past the last
-// whole piece
-template <bool NTL, bool NTS>
-__device__ __forceinline__ void copy_row(const u32x4 *s16, u32x4 *d16, int n16, int lane)
-{
-    const int nfull = n16 / kWave;
-    const u32x4 *s = s16 + lane;
-    u32x4 *d = d16 + lane;
-    int c = 0;
-    for (; c + 8 <= nfull; c += 8) copy_pieces<8, NTL, NTS>(s + c * kWave, d + c * kWave);
-    switch (nfull - c) {
-        case 7: copy_pieces<7, NTL, NTS>(s + c * kWave, d + c * kWave); break;
-        case 6: copy_pieces<6, NTL, NTS>(s + c * kWave, d + c * kWave); break;
-        case 5: copy_pieces<5, NTL, NTS>(s + c * kWave, d + c * kWave); break;
-        case 4: copy_pieces<4, NTL, NTS>(s + c * kWave, d + c * kWave); break;
-        case 3: copy_pieces<3, NTL, NTS>(s + c * kWave, d + c * kWave); break;
-        case 2: copy_pieces<2, NTL, NTS>(s + c * kWave, d + c * kWave); break;
-        case 1: copy_pieces<1, NTL, NTS>(s + c * kWave, d + c * kWave); break;
-        default: break;
-    }
-    const int tail = nfull * kWave + lane;
-    if (tail < n16) {
-        const u32x4 v = NTL ? __builtin_nontemporal_load(s16 + tail) : s16[tail];
-        if (NTS) __builtin_nontemporal_store(v, d16 + tail);
-        else d16[tail] = v;
-    }
-}
-
-// The same copy with WRITE-THROUGH stores (sc0 sc1: the bytes leave every cache level on their way to the destination, local or remote):
-// for rows that another workgroup of the SAME launch announces to a peer -- the announcing lane then needs no release fence, only this
-// wave's vmcnt drain before the workgroup counts itself in (combine_push_kernel's tail).  Stores through a buffer descriptor on the
-// wave-uniform row base: the compiler counts them (raw_buffer_store aux: sc0 = 1, sc1 = 16).
-typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int wt_u32x4;
-template <int N, bool NTL>
-__device__ __forceinline__ void copy_pieces_wt(const u32x4 *s, __amdgpu_buffer_rsrc_t d, uint32_t off)
-{
-    u32x4 v[N];
-#pragma unroll
-    for (int u = 0; u < N; ++u) v[u] = NTL ? __builtin_nontemporal_load(s + u * kWave) : s[u * kWave];
-#pragma unroll
-    for (int u = 0; u < N; ++u)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wt_u32x4, v[u]), d, (int)(off + (uint32_t)u * (kWave * 16u)), 0, 17);
-}
-template <bool NTL>
-__device__ __forceinline__ void copy_row_wt(const u32x4 *s16, void *d_row /* wave-uniform */, int n16, int lane)
-{
-    const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uint64_t)(uintptr_t)d_row >> 32)) << 32) |
-                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)d_row);
-    const __amdgpu_buffer_rsrc_t d = __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)base, 0, n16 * 16, 0x00020000);
-    const int nfull = n16 / kWave;
-    const u32x4 *s = s16 + lane;
-    const uint32_t l16 = (uint32_t)lane * 16u;
-    int c = 0;
-    for (; c + 8 <= nfull; c += 8) copy_pieces_wt<8, NTL>(s + c * kWave, d, l16 + (uint32_t)c * (kWave * 16u));
-    switch (nfull - c) {
-        case 7: copy_pieces_wt<7, NTL>(s + c * kWave, d, l16 + (uint32_t)c * (kWave * 16u)); break;
-        case 6: copy_pieces_wt<6, NTL>(s + c * kWave, d, l16 + (uint32_t)c * (kWave * 16u)); break;
-        case 5: copy_pieces_wt<5, NTL>(s + c * kWave, d, l16 + (uint32_t)c * (kWave * 16u)); break;
-        case 4: copy_pieces_wt<4, NTL>(s + c * kWave, d, l16 + (uint32_t)c * (kWave * 16u)); break;
-        case 3: copy_pieces_wt<3, NTL>(s + c * kWave, d, l16 + (uint32_t)c * (kWave * 16u)); break;
-        case 2: copy_pieces_wt<2, NTL>(s + c * kWave, d, l16 + (uint32_t)c * (kWave * 16u)); break;
-        case 1: copy_pieces_wt<1, NTL>(s + c * kWave, d, l16 + (uint32_t)c * (kWave * 16u)); break;
-        default: break;
-    }
-    const int tail = nfull * kWave + lane;
-    if (tail < n16) {
-        const u32x4 v = NTL ? __builtin_nontemporal_load(s16 + tail) : s16[tail];
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wt_u32x4, v), d, tail * 16, 0, 17);
-    }
-}
-
-// Rows that a PEER announces from inside its own launch (a tag / flag word stored behind the drained write-through payload) and that a
-// wave of a RUNNING launch reads right after it saw that word: the payload is read with SYSTEM-scope loads (sc0 sc1, the scope of the
-// poll itself), through a buffer descriptor on the wave-uniform row base.  No cache level may answer such a load with a line it kept
-// from an earlier call on the same ping-pong half (or, where neighbouring rows share a 128-byte line, from a neighbour's read), which a
-// plain / nontemporal load does not promise; no acquire fence (a cache invalidate per wave) is needed either.  aux: sc0 = 1, sc1 = 16.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t sys_row_rsrc(const void *row /* wave-uniform */, int bytes)
+// Buffer descriptor over one row at a wave-uniform address: its base is read from the first lane, so the compiler keeps it in SGPRs.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void *row /* wave-uniform */, int bytes)
 {
     const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((uint64_t)(uintptr_t)row >> 32)) << 32) |
                           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)row);
     return __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)base, 0, bytes, 0x00020000);
 }
+
+// How a wave reads and writes the items of a row (item i: bytes [i * sizeof(V), (i + 1) * sizeof(V)), loads 16 bytes).  NT: nontemporal.
+// LdSys: SYSTEM-scope loads (sc0 sc1) through a descriptor on the row -- for rows that a PEER announces from inside its own launch (a
+// tag / flag word stored behind the drained write-through payload) and that a wave of a RUNNING launch reads right after it saw that
+// word.  No cache level may answer such a load with a line it kept from an earlier call on the same ping-pong half (or, where
+// neighbouring rows share a 128-byte line, from a neighbour's read), which a plain / nontemporal load does not promise; no acquire
+// fence (a cache invalidate per wave) is needed either.
+// StWT: WRITE-THROUGH stores (sc0 sc1: the bytes leave every cache level on their way to the destination, local or remote) through
+// a descriptor on the row -- for rows that another workgroup of the SAME launch announces to a peer: the announcing lane then needs
+// no release fence, only this wave's vmcnt drain before the workgroup counts itself in.  The compiler counts buffer stores.
+// at(n): the same policy n 16-byte items further on.  The copy moves its base once per lane and per piece group and indexes inside a
+// group by constants, so those land in the instructions' offset fields (indexing from the row start cost 64-bit address arithmetic).
+template <bool NT>
+struct LdMem {
+    const u32x4 *p;
+    __device__ __forceinline__ LdMem at(int n) const { return LdMem{p + n}; }
+    __device__ __forceinline__ u32x4 operator()(int i) const { return NT ? __builtin_nontemporal_load(p + i) : p[i]; }
+};
 __device__ __forceinline__ u32x4 ld_sys_b128(__amdgpu_buffer_rsrc_t r, uint32_t byte_off)
 {
     return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 17));
 }
-template <int N, bool NTS>
-__device__ __forceinline__ void copy_pieces_sys(__amdgpu_buffer_rsrc_t s, uint32_t off, u32x4 *d)
+struct LdSys {
+    __amdgpu_buffer_rsrc_t r;
+    uint32_t off;
+    __device__ __forceinline__ LdSys at(int n) const { return LdSys{r, off + (uint32_t)n * 16u}; }
+    __device__ __forceinline__ u32x4 operator()(int i) const { return ld_sys_b128(r, off + (uint32_t)i * 16u); }
+};
+template <bool NT>
+struct StMem {
+    u32x4 *p;
+    __device__ __forceinline__ StMem at(int n) const { return StMem{p + n}; }
+    template <class V>
+    __device__ __forceinline__ void operator()(int i, const V &v) const
+    {
+        if (NT) __builtin_nontemporal_store(v, (V *)p + i);
+        else ((V *)p)[i] = v;
+    }
+};
+typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int wt_u32x4;
+struct StWT {
+    __amdgpu_buffer_rsrc_t r;
+    uint32_t off;
+    __device__ __forceinline__ StWT at(int n) const { return StWT{r, off + (uint32_t)n * 16u}; }
+    template <class V>
+    __device__ __forceinline__ void operator()(int i, const V &v) const
+    {
+        static_assert(sizeof(V) == 16, "write-through stores are 16-byte items");
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wt_u32x4, v), r, (int)(off + (uint32_t)i * 16u), 0, 17);
+    }
+};
+
+// ---- row copy by one wave.  N pieces of 1 KB (lane l moves item 64 u + l, u < N): all loads back to back, then all stores, in
+// straight-line code.  Written as `for u < 8: if (item < n16) v[u] = load(...)` the compiler gave every load and every store its own
+// block with an s_waitcnt vmcnt(0) in front of it: sixteen serial round trips per 8 KB, each store waiting for the (possibly remote)
+// acknowledgement of the one before (combine_push, pull_indexed and the low-latency pull were all compiled that way).
+template <int N, class Ld, class St>
+__device__ __forceinline__ void copy_pieces(const Ld &ld, const St &st)
 {
     u32x4 v[N];
 #pragma unroll
-    for (int u = 0; u < N; ++u) v[u] = ld_sys_b128(s, off + (uint32_t)u * (kWave * 16u));
+    for (int u = 0; u < N; ++u) v[u] = ld(u * kWave);
 #pragma unroll
-    for (int u = 0; u < N; ++u) {
-        if (NTS) __builtin_nontemporal_store(v[u], d + u * kWave);
-        else d[u * kWave] = v[u];
-    }
+    for (int u = 0; u < N; ++u) st(u * kWave, v[u]);
 }
-template <bool NTS>
-__device__ __forceinline__ void copy_row_sys(const void *s_row /* wave-uniform */, u32x4 *d16, int n16, int lane)
+// a row of n16 16-byte items: whole pieces in groups of up to eight (the group size is wave-uniform), then the items past the last
+// whole piece
+template <class Ld, class St>
+__device__ __forceinline__ void copy_row_by(const Ld &ld, const St &st, int n16, int lane)
 {
-    const __amdgpu_buffer_rsrc_t s = sys_row_rsrc(s_row, n16 * 16);
     const int nfull = n16 / kWave;
-    u32x4 *d = d16 + lane;
-    const uint32_t l16 = (uint32_t)lane * 16u;
+    const Ld l = ld.at(lane);
+    const St s = st.at(lane);
     int c = 0;
-    for (; c + 8 <= nfull; c += 8) copy_pieces_sys<8, NTS>(s, l16 + (uint32_t)c * (kWave * 16u), d + c * kWave);
+    for (; c + 8 <= nfull; c += 8) copy_pieces<8>(l.at(c * kWave), s.at(c * kWave));
     switch (nfull - c) {
-        case 7: copy_pieces_sys<7, NTS>(s, l16 + (uint32_t)c * (kWave * 16u), d + c * kWave); break;
-        case 6: copy_pieces_sys<6, NTS>(s, l16 + (uint32_t)c * (kWave * 16u), d + c * kWave); break;
-        case 5: copy_pieces_sys<5, NTS>(s, l16 + (uint32_t)c * (kWave * 16u), d + c * kWave); break;
-        case 4: copy_pieces_sys<4, NTS>(s, l16 + (uint32_t)c * (kWave * 16u), d + c * kWave); break;
-        case 3: copy_pieces_sys<3, NTS>(s, l16 + (uint32_t)c * (kWave * 16u), d + c * kWave); break;
-        case 2: copy_pieces_sys<2, NTS>(s, l16 + (uint32_t)c * (kWave * 16u), d + c * kWave); break;
-        case 1: copy_pieces_sys<1, NTS>(s, l16 + (uint32_t)c * (kWave * 16u), d + c * kWave); break;
+        case 7: copy_pieces<7>(l.at(c * kWave), s.at(c * kWave)); break;
+        case 6: copy_pieces<6>(l.at(c * kWave), s.at(c * kWave)); break;
+        case 5: copy_pieces<5>(l.at(c * kWave), s.at(c * kWave)); break;
+        case 4: copy_pieces<4>(l.at(c * kWave), s.at(c * kWave)); break;
+        case 3: copy_pieces<3>(l.at(c * kWave), s.at(c * kWave)); break;
+        case 2: copy_pieces<2>(l.at(c * kWave), s.at(c * kWave)); break;
+        case 1: copy_pieces<1>(l.at(c * kWave), s.at(c * kWave)); break;
         default: break;
     }
     const int tail = nfull * kWave + lane;
-    if (tail < n16) {
-        const u32x4 v = ld_sys_b128(s, (uint32_t)tail * 16u);
-        if (NTS) __builtin_nontemporal_store(v, d16 + tail);
-        else d16[tail] = v;
+    if (tail < n16) st(tail, ld(tail));
+}
+template <bool NTL, bool NTS>
+__device__ __forceinline__ void copy_row(const u32x4 *s16, u32x4 *d16, int n16, int lane)
+{
+    copy_row_by(LdMem<NTL>{s16}, StMem<NTS>{d16}, n16, lane);
+}
+// write-through stores (StWT) to a wave-uniform destination row
+template <bool NTL>
+__device__ __forceinline__ void copy_row_wt(const u32x4 *s16, void *d_row /* wave-uniform */, int n16, int lane)
+{
+    copy_row_by(LdMem<NTL>{s16}, StWT{row_rsrc(d_row, n16 * 16), 0u}, n16, lane);
+}
+// system-scope loads (LdSys) from a wave-uniform source row
+template <bool NTS>
+__device__ __forceinline__ void copy_row_sys(const void *s_row /* wave-uniform */, u32x4 *d16, int n16, int lane)
+{
+    copy_row_by(LdSys{row_rsrc(s_row, n16 * 16), 0u}, StMem<NTS>{d16}, n16, lane);
+}
+
+// segment of row r: the first i in [0, n) with cum[i] > r, for an inclusive cumsum cum of n segment sizes (n - 1 when there is none)
+__device__ __forceinline__ int seg_of(const int32_t *cum, int n, long long r)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cum[mid] > r) hi = mid; else lo = mid + 1;
     }
+    return lo;
 }
 
 // 8-byte words other GPUs write/poll: always system-scope atomics, never plain accesses.
@@ -281,6 +263,17 @@ __device__ __forceinline__ void report_status(int32_t *status, int32_t code)
 
 // ~100 MHz constant-rate counter (s_memrealtime); used only to bound spins.
 __device__ __forceinline__ uint64_t ticks_100mhz() { return wall_clock64(); }
+
+// PeerPtrs from W host pointers; false when one of them is null
+template <class P>
+inline bool peer_ptrs(P *const *host, int W, PeerPtrs &pp)
+{
+    for (int i = 0; i < W; ++i) {
+        if (!host[i]) return false;
+        pp.p[i] = (void *)host[i];
+    }
+    return true;
+}
 
 inline int launch_status()
 {

@@ -628,7 +628,7 @@ __global__ __launch_bounds__(256) void selftest_inlaunch_kernel(InLaunchTest a, 
         for (int row = wave; row < 2 * kILRows; row += (int)blockDim.x / kWave) {
             const bool flagged = row >= kILRows;
             uint8_t *rp = flagged ? base + (size_t)kILRows * kILTagStride + (size_t)(row - kILRows) * kILFlagStride : base + (size_t)row * kILTagStride;
-            const __amdgpu_buffer_rsrc_t rs = sys_row_rsrc(rp, kILPayload + 16);
+            const __amdgpu_buffer_rsrc_t rs = row_rsrc(rp, kILPayload + 16);
             if (!a.skip_payload) {
 #pragma unroll
                 for (int u = 0; u < kILPayload / (kWave * 16); ++u) {
@@ -675,7 +675,7 @@ __global__ __launch_bounds__(256) void selftest_inlaunch_kernel(InLaunchTest a, 
         }
         asm volatile("" ::: "memory");                         // the wave reconverges behind lane 0's wait: the row is read after its word was seen
         if (__builtin_amdgcn_readfirstlane(late)) continue;
-        const __amdgpu_buffer_rsrc_t rs = sys_row_rsrc(rp, kILPayload);
+        const __amdgpu_buffer_rsrc_t rs = row_rsrc(rp, kILPayload);
         u32x4 v[kILPayload / (kWave * 16)];
 #pragma unroll
         for (int u = 0; u < kILPayload / (kWave * 16); ++u) v[u] = ld_sys_b128(rs, (uint32_t)(u * kWave + lane) * 16u);
