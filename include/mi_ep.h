@@ -290,6 +290,21 @@ int mi_ep_dispatch_stage_local(const void *x, const void *topk_idx, int idx_is_i
                                const int32_t *recv_count, const int32_t *num_tokens_per_expert, int num_tokens, int num_topk,
                                int hidden, int num_experts, int quant_mode, int rows_hint, void *recv_x, float *recv_x_scales,
                                int32_t *recv_src_idx, int32_t *local_row_out, void *stream);
+/* num_ranks == 1 only: mi_ep_dispatch_stage_local without the notify launch in front of it.  Workgroup 0 of the same launch writes
+ * cnt_matrix = [num_tokens_per_expert[0..E), num_tokens], derives from it the nine tables of mi_ep_notify_tables (W = 1, my_rank = 0,
+ * relative_pull) and, when summary_host is not NULL, the host summary words (total, max batch, per-expert counts -- unordered, as there);
+ * when epoch_ctr is not NULL it moves the dispatch call counter on as mi_ep_notify_exchange_tables does (reads *epoch_ctr, stores
+ * *epoch_ctr + 1).  The token workgroups come after it; each takes the exclusive prefix of num_tokens_per_expert at e from its own scan
+ * of the counts, so the receive rows, scales, triples and local_row_out are byte for byte those of mi_ep_notify_tables +
+ * mi_ep_dispatch_stage_local.  E <= 2048.  With num_tokens == 0 or rows_hint <= 0 the launch is workgroup 0 alone (x, topk_idx,
+ * send_token_idx_small, recv_x and recv_src_idx may then be NULL).  Unlike mi_ep_dispatch_stage_local it must run once per call. */
+int mi_ep_dispatch_stage_local_tables(const void *x, const void *topk_idx, int idx_is_i32, const int32_t *send_token_idx_small,
+                                      const int32_t *num_tokens_per_expert, int num_tokens, int num_topk, int hidden, int num_experts,
+                                      int quant_mode, int rows_hint, void *recv_x, float *recv_x_scales, int32_t *recv_src_idx,
+                                      int32_t *local_row_out, int relative_pull, int32_t *cnt_matrix, int32_t *recv_count,
+                                      int32_t *recv_offset, int32_t *recv_tokens_per_expert, int32_t *expert_global_offset,
+                                      int32_t *srcrank_in_expert_offset, int32_t *r_in_srcrank_offset, int32_t *total_recv_token,
+                                      int32_t *max_bs, int32_t *pull_offset, int32_t *summary_host, uint64_t *epoch_ctr, void *stream);
 
 /* Push transport of normal dispatch (selectable next to the pull above; the same received bytes).  The sender writes the
  * quantised row of token t ONCE into the window of every rank that owns at least one of the token's experts (the reference

@@ -509,9 +509,12 @@ void Buffer::clean_low_latency_buffer(int, int, int) {}   // no-op, as in the re
 // this rank's counts + "rows staged" flag, collects everybody's and derives the tables.  The call's epoch and ping-pong
 // half come from the device-resident counter of the family (see include/mi_ep.h), so nothing here depends on how many
 // calls ran before.  stage_local (num_ranks == 1 only): no staging launch -- dispatch_pull then quantises x straight into the
-// receive rows (mi_ep_dispatch_stage_local); the notify exchange still runs, its tables and the host summary are needed either way.
+// receive rows (mi_ep_dispatch_stage_local); the notify exchange still runs, its tables and the host summary are needed either way --
+// unless local_tables: then no notify launch runs at all, and the stage_local launch of dispatch_pull builds the tables, the summary
+// and the call counter step itself (mi_ep_dispatch_stage_local_tables; ONE dispatch_pull per exchange).
 Buffer::DispatchExchange Buffer::dispatch_exchange(const at::Tensor &x, const at::Tensor &topk_idx, const Layout &lay, int E, int qm,
-                                                   bool want_summary, int32_t *wait_stats, hipStream_t st, bool stage_local)
+                                                   bool want_summary, int32_t *wait_stats, hipStream_t st, bool stage_local,
+                                                   bool local_tables)
 {
     const int T = (int)x.size(0), H = (int)x.size(1), K = (int)topk_idx.size(1), W = (int)num_ranks, L = E / W;
     const size_t rb = mi_ep_dispatch_row_bytes(H, qm);
@@ -531,7 +534,9 @@ Buffer::DispatchExchange Buffer::dispatch_exchange(const at::Tensor &x, const at
     auto region_peers = peer_family_bases(kDispatch);
     const bool i32idx = topk_idx.scalar_type() == at::kInt;
     EP_HOST_ASSERT(!stage_local || W == 1);
+    EP_HOST_ASSERT(!local_tables || (stage_local && !wait_stats));
     ex.stage_local = stage_local;
+    ex.local_tables = local_tables;
     if (!stage_local) { ProfScope ps_(this, ex.push ? "dispatch_stage_push" : "dispatch_stage", st);
       if (ex.push)
           MI_EP_CHECK(mi_ep_dispatch_stage_push(x.data_ptr(), topk_idx.data_ptr(), i32idx, lay.send_token_idx_small.data_ptr<int>(),
@@ -549,7 +554,8 @@ Buffer::DispatchExchange Buffer::dispatch_exchange(const at::Tensor &x, const at
         for (int i = 2 + L - 1; i >= 1; --i) __atomic_store_n(summary_host + i, -1, __ATOMIC_RELAXED);
         __atomic_store_n(summary_host, -1, __ATOMIC_RELEASE);
     }
-    { ProfScope ps_(this, "dispatch_notify", st);
+    if (local_tables) ex.summary = want_summary ? summary_dev : nullptr;
+    else { ProfScope ps_(this, "dispatch_notify", st);
       MI_EP_CHECK(mi_ep_notify_exchange_tables((uint64_t *const *)notify_peers.data(), (uint64_t *const *)flag_peers.data(),
                                                lay.num_tokens_per_expert.data_ptr<int>(), T, (const uint64_t *)(window + kOffNotify), 0,
                                                (const uint64_t *)(window + kOffFlags + kFlagDispatch * kFlagGroupSlots * 8), 0,
@@ -589,7 +595,17 @@ void Buffer::dispatch_pull(const DispatchExchange &ex, int H, int K, int L, int 
     at::Tensor local_row_out;
     if (local && num_ranks == 1 && combine_local_rows_enabled && ex.num_tokens > 0)
         local_row_out = at::empty({(int64_t)ex.num_tokens * K}, at::dtype(at::kInt).device(dev));
-    if (ex.stage_local && ex.num_tokens > 0)        // (reads x and the tables only: a second, exact-size call writes the same rows again)
+    if (ex.local_tables) {            // (also with no tokens: workgroup 0 still writes the tables, the summary and the call counter)
+        const NotifyTables &nt = ex.nt;
+        MI_EP_CHECK(mi_ep_dispatch_stage_local_tables(
+            ex.x.data_ptr(), ex.topk_idx.data_ptr(), ex.topk_idx.scalar_type() == at::kInt, ex.send_token_idx_small.data_ptr<int>(),
+            ex.num_tokens_per_expert.data_ptr<int>(), ex.num_tokens, K, H, ex.num_experts, qm, (int)rows_alloc, rx.data_ptr(),
+            quant ? (float *)rs.data_ptr() : nullptr, src_idx.data_ptr<int>(), local_row_out.defined() ? local_row_out.data_ptr<int>() : nullptr,
+            ex.push ? 1 : 0, nt.cnt.data_ptr<int>(), nt.recv_count.data_ptr<int>(), nt.recv_offset.data_ptr<int>(),
+            nt.recv_tokens_per_expert.data_ptr<int>(), nt.expert_global_offset.data_ptr<int>(), nt.srcrank_in_expert_offset.data_ptr<int>(),
+            nt.r_in_srcrank_offset.data_ptr<int>(), nt.total_recv_token.data_ptr<int>(), nt.max_bs.data_ptr<int>(),
+            nt.pull_offset.data_ptr<int>(), ex.summary, epoch_ctr(kDispatch), st));
+    } else if (ex.stage_local && ex.num_tokens > 0)        // (reads x and the tables only: a second, exact-size call writes the same rows again)
         MI_EP_CHECK(mi_ep_dispatch_stage_local(ex.x.data_ptr(), ex.topk_idx.data_ptr(), ex.topk_idx.scalar_type() == at::kInt,
                                                ex.send_token_idx_small.data_ptr<int>(), ex.nt.recv_count.data_ptr<int>(),
                                                ex.num_tokens_per_expert.data_ptr<int>(), ex.num_tokens, K, H, ex.num_experts, qm,
@@ -668,17 +684,21 @@ Buffer::intranode_dispatch(const at::Tensor &x, const std::optional<at::Tensor> 
     const bool host_sync = num_worst_tokens <= 0;
     // one rank, own rows gathered token-wise: nobody else reads the staged rows, so the pull quantises x itself (no staging launch)
     const bool stage_local = W == 1 && dispatch_local_rows && dispatch_stage_local;
-    DispatchExchange ex = dispatch_exchange(x, *topk_idx, lay, E, qm, host_sync, wait_stats, st, stage_local);
+    static const bool speculate = get_value_from_env("DEEPEP_SPECULATIVE_RECV", 1) != 0;
+    // ... and when the receive buffers can be sized before the row count is known, that launch builds the count tables itself: no
+    // notify launch.  At one rank the received rows never exceed T * K, so the host-synced form allocates that many up front (one pull,
+    // never a retry); num_worst_tokens sizes them in the graph-friendly form.
+    const bool local_tables = stage_local && dispatch_local_tables && !wait_stats && (!host_sync || speculate);
+    DispatchExchange ex = dispatch_exchange(x, *topk_idx, lay, E, qm, host_sync, wait_stats, st, stage_local, local_tables);
 
     // Receive buffers + the pull launch.  The exact row count reaches the host only through the pinned summary word;
     // to keep the GPU busy across that round trip the pull is launched FIRST into buffers sized from the previous call
     // (+25 %), and the results are returned as exact-size prefixes once the host knows the count.  A call that receives
     // more than the guess simply pulls again into exact-size buffers (the kernel never writes past `rows_hint`).
     at::Tensor expandx_out, dynamic_scales_out, expand_idx_out;
-    static const bool speculate = get_value_from_env("DEEPEP_SPECULATIVE_RECV", 1) != 0;
     int64_t guess = 0;
-    if (host_sync && speculate && last_recv_rows > 0) {
-        guess = last_recv_rows + last_recv_rows / 4 + 256;
+    if (host_sync && (local_tables || (speculate && last_recv_rows > 0))) {
+        guess = local_tables ? std::max<int64_t>((int64_t)T * K, 1) : last_recv_rows + last_recv_rows / 4 + 256;
         dispatch_pull(ex, H, K, L, qm, guess, x.options(), expandx_out, dynamic_scales_out, expand_idx_out, st);
     }
     // Everything the host can prepare without the row count is prepared BEFORE it waits for it: the wait ends when the notify kernel
@@ -727,6 +747,7 @@ Buffer::intranode_dispatch(const at::Tensor &x, const std::optional<at::Tensor> 
         dynamic_scales_out = dynamic_scales_out.narrow(0, 0, quant_is_mx(qm) ? rows * (H / 32) : rows);
         expand_idx_out = expand_idx_out.narrow(0, 0, rows * 3);
     } else {
+        EP_HOST_ASSERT(!local_tables || !host_sync);      // (one pull per exchange: T * K rows always hold a one-rank call)
         dispatch_pull(ex, H, K, L, qm, rows, x.options(), expandx_out, dynamic_scales_out, expand_idx_out, st);
     }
     std::optional<at::Tensor> recv_topk_idx, recv_topk_weights;                                // allocated, never written

@@ -54,6 +54,12 @@ public:
     // pull_local).  Results are identical either way.
     void set_dispatch_stage_local(bool on) { dispatch_stage_local = on; }
     bool get_dispatch_stage_local() const { return dispatch_stage_local; }
+    // MI355X only, num_ranks == 1 with stage_local: the count tables come from workgroup 0 of the stage_local launch
+    // (mi_ep_dispatch_stage_local_tables) and no notify launch runs, when the receive buffers can be sized before the count is known
+    // (num_worst_tokens, or DEEPEP_SPECULATIVE_RECV on) and no wait statistics are asked for.  Default from MI_EP_DISPATCH_LOCAL_TABLES
+    // (0 = notify launch + stage_local).  Results are identical either way.
+    void set_dispatch_local_tables(bool on) { dispatch_local_tables = on; }
+    bool get_dispatch_local_tables() const { return dispatch_local_tables; }
     // MI355X only: fused_deep_moe / dispatch_ffn_combine at prefill sizes multiply the staged token rows in place (a row-offset table) instead
     // of a K-fold gathered copy; default from MI_EP_FUSED_GATHER (0 = gather).  Results are identical either way.
     // MI355X only: GEMM1 of fused_deep_moe / dispatch_ffn_combine requantises its rows in its epilogue (mi_ep_moe_gemm1_swiglu_quant) instead
@@ -274,10 +280,15 @@ private:
         // stage_local: nothing was staged; the pull reads the token rows from x (mi_ep_dispatch_stage_local)
         at::Tensor x;
         bool stage_local = false;
+        // local_tables (stage_local only): no notify launch ran; the stage_local launch builds the tables and the summary
+        // (summary = NULL: no host words)
+        bool local_tables = false;
+        int32_t *summary = nullptr;
         int num_tokens = 0, num_experts = 0;
     };
     DispatchExchange dispatch_exchange(const at::Tensor &x, const at::Tensor &topk_idx, const Layout &lay, int E, int qm,
-                                       bool want_summary, int32_t *wait_stats, hipStream_t st, bool stage_local = false);
+                                       bool want_summary, int32_t *wait_stats, hipStream_t st, bool stage_local = false,
+                                       bool local_tables = false);
     void dispatch_pull(const DispatchExchange &ex, int H, int K, int L, int qm, int64_t rows_alloc, const at::TensorOptions &x_opts,
                        at::Tensor &rx, at::Tensor &rs, at::Tensor &src_idx, hipStream_t st);
     at::Tensor combine_finish(const at::Tensor &topk_idx, const float *topk_weights, int H, int E, const at::TensorOptions &opts,
@@ -311,6 +322,7 @@ private:
     bool dispatch_local_rows = !(getenv("MI_EP_DISPATCH_LOCAL") && atoi(getenv("MI_EP_DISPATCH_LOCAL")) == 0);
     bool combine_local_rows_enabled = !(getenv("MI_EP_COMBINE_LOCAL") && atoi(getenv("MI_EP_COMBINE_LOCAL")) == 0);
     bool dispatch_stage_local = !(getenv("MI_EP_DISPATCH_STAGE_LOCAL") && atoi(getenv("MI_EP_DISPATCH_STAGE_LOCAL")) == 0);
+    bool dispatch_local_tables = !(getenv("MI_EP_DISPATCH_LOCAL_TABLES") && atoi(getenv("MI_EP_DISPATCH_LOCAL_TABLES")) == 0);
     bool fused_rows_in_place = !(getenv("MI_EP_FUSED_GATHER") && atoi(getenv("MI_EP_FUSED_GATHER")) == 0);
     bool fused_requant = getenv("MI_EP_FUSED_REQUANT") && atoi(getenv("MI_EP_FUSED_REQUANT")) != 0;
     int gemm_xcds = 1;

@@ -68,6 +68,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     MI_METHOD(buf, get_local_row_paths);
     MI_METHOD(buf, set_dispatch_stage_local);
     MI_METHOD(buf, get_dispatch_stage_local);
+    MI_METHOD(buf, set_dispatch_local_tables);
+    MI_METHOD(buf, get_dispatch_local_tables);
     MI_METHOD(buf, set_fused_rows_in_place);
     MI_METHOD(buf, get_fused_rows_in_place);
     MI_METHOD(buf, get_num_rdma_ranks);

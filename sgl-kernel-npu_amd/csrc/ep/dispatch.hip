@@ -23,6 +23,7 @@
 
 #include "ep_common.h"
 #include "layout_dev.h"
+#include "notify_tables.h"
 
 namespace mi_ep {
 
@@ -948,23 +949,86 @@ __global__ __launch_bounds__(kWave * kPullWaves) void pull_local_kernel(
     }
 }
 
+// The W = 1 count tables of the one-launch form (mi_ep_dispatch_stage_local_tables): what notify_wait_tables_kernel derives at one
+// rank, written by workgroup 0 of stage_local_kernel<..., TABLES = true>.
+struct LocalTables {
+    int32_t *cnt_matrix, *recv_count, *recv_offset, *recv_tokens_per_expert, *expert_global_offset, *srcrank_in_expert_offset,
+        *r_in_srcrank_offset, *total_recv_token, *max_bs, *pull_offset;
+    int32_t *summary_host;                        // NULL: no host words
+    uint64_t *epoch_ctr;                          // NULL: no call counter
+    int relative_pull;
+};
+
+// Exclusive prefix sum of cnt[0..E) at index e, returned to every lane with 0 <= e < E (others: unspecified).  One wave, 64 counts per
+// step: a DPP scan of the step, then a bpermute from the lane that holds e.  Wave-uniform control flow, all 64 lanes active.
+__device__ __forceinline__ int32_t wave_excl_prefix_at(const int32_t *__restrict__ cnt, int E, int e)
+{
+    constexpr int kSteps = 4;                                     // loads in flight per round: E <= 256 in one
+    const int lane = lane_id();
+    int32_t carry = 0, at = 0;
+    for (int b = 0; b < E; b += kWave * kSteps) {
+        const int32_t *c = cnt + b;                               // (uniform base: the lanes address it with 32-bit offsets)
+        int32_t v[kSteps];
+#pragma unroll
+        for (int u = 0; u < kSteps; ++u) {                        // clamped, unconditional loads: no branch around each one
+            const int i = u * kWave + lane;
+            const int32_t c_i = c[min(i, E - 1 - b)];
+            v[u] = i < E - b ? c_i : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < kSteps; ++u) {                        // the exclusive prefix at e = the inclusive one at e - 1
+            v[u] = wave_incl_scan_i32(v[u]);
+            const int d = e - (b + u * kWave);
+            const int32_t prev = __builtin_amdgcn_ds_bpermute((d - 1) << 2, v[u]);
+            if ((unsigned)d < (unsigned)kWave) at = carry + (d ? prev : 0);
+            carry += __builtin_amdgcn_readlane(v[u], kWave - 1);
+        }
+    }
+    return at;
+}
+
+// Workgroup 0 of the one-launch form: the W = 1 count row [cnt[0..E), T] goes to cnt_matrix, the call counter moves on exactly as in
+// notify_wait_tables_kernel (read *ctr, store *ctr + 1), and notify_tables_body derives the nine tables and the host's summary words
+// from the row.  The body reads the row back from cnt_matrix (written by this workgroup, ordered by the barrier): an LDS copy next to
+// the body's 3E + 3 words of scratch would take 32 KB at E = 2048 and cost the row workgroups one resident workgroup per CU.
+__device__ void stage_local_tables(const int32_t *__restrict__ tokens_per_expert, int T, int E, const LocalTables &tb)
+{
+    extern __shared__ __attribute__((aligned(16))) int32_t sm[];
+    for (int i = threadIdx.x; i <= E; i += blockDim.x) tb.cnt_matrix[i] = i < E ? tokens_per_expert[i] : T;
+    if (tb.epoch_ctr && threadIdx.x == 0) *tb.epoch_ctr = *tb.epoch_ctr + 1;
+    __syncthreads();
+    notify_tables_body(tb.cnt_matrix, 1, E, 0, tb.relative_pull, tb.recv_count, tb.recv_offset, tb.recv_tokens_per_expert,
+                       tb.expert_global_offset, tb.srcrank_in_expert_offset, tb.r_in_srcrank_offset, tb.total_recv_token, tb.max_bs,
+                       tb.pull_offset, tb.summary_host, sm);
+}
+
 // Single-rank dispatch in one pass (mi_ep_dispatch_stage_local): the token row is read from x, quantised in registers by the same
 // code as stage_body (ld_row_items + quant_row; bf16: ld_row_chunks, a plain copy) and stored straight to each of its selections'
 // receive rows, with the scale and (0, t, k) triple -- the bytes stage_compact + pull_local_kernel produce at num_ranks == 1, without
 // the staged row in between (T * (H + 16) bytes written, then read back, and one launch).  Output row of selection (t, k):
 // recv_count[e] - num_tokens_per_expert[e] + send_token_idx_small[t, k]; rows below row_capacity only; the write-back / nontemporal
 // split of pull_local_kernel (pull_nt_from_row).  One wave per token, kStageWaves tokens per workgroup.
-template <bool I32, int QM, bool NT>
+// TABLES (mi_ep_dispatch_stage_local_tables): no notify launch before this one.  Workgroup 0 builds the count tables
+// (stage_local_tables), the token workgroups follow it, and each wave takes recv_count[e] - num_tokens_per_expert[e] -- the exclusive
+// prefix of the counts at e -- from its own scan of the counts (wave_excl_prefix_at), whose loads go out with the routing loads right
+// behind the row's: no load that depends on e is left for after the row has arrived.
+template <bool I32, int QM, bool NT, bool TABLES>
 __global__ __launch_bounds__(kWave * kStageWaves) void stage_local_kernel(
     const uint16_t *__restrict__ x, const void *__restrict__ topk_idx, const int32_t *__restrict__ idx_small,
     const int32_t *__restrict__ recv_count, const int32_t *__restrict__ tokens_per_expert, int T, int K, int H, int E,
     uint8_t *__restrict__ recv_x, float *__restrict__ recv_scales, int32_t *__restrict__ recv_src_idx, int row_capacity,
-    int nt_from_row, int32_t *__restrict__ local_row_out)
+    int nt_from_row, int32_t *__restrict__ local_row_out, LocalTables tb)
 {
     constexpr bool kQuant = QM != MI_EP_QUANT_NONE, kMx = quant_is_mx(QM);
     constexpr int kIt = kQuant ? kMaxItems : kChunkItems;
+    if constexpr (TABLES) {
+        if (blockIdx.x == 0) {                                    // the whole workgroup, before any per-wave return
+            stage_local_tables(tokens_per_expert, T, E, tb);
+            return;
+        }
+    }
     const int lane = lane_id();
-    const int t = __builtin_amdgcn_readfirstlane(blockIdx.x * kStageWaves + threadIdx.x / kWave);
+    const int t = __builtin_amdgcn_readfirstlane((blockIdx.x - (TABLES ? 1 : 0)) * kStageWaves + threadIdx.x / kWave);
     if (t >= T) return;
     // the row is requested before the routing is known (its three dependent loads run under the row's latency)
     u32x4 raw[kQuant ? kMaxItems : 1][2];
@@ -972,11 +1036,25 @@ __global__ __launch_bounds__(kWave * kStageWaves) void stage_local_kernel(
     if constexpr (kQuant) ld_row_items(x, t, H, raw);
     else ld_row_chunks(x, t, H, q);
     int r_l = -1;
-    if (lane < K) {
-        const long long e = ld_idx<I32>(topk_idx, (long long)t * K + lane);
-        if (e >= 0 && e < E) {
-            const int r = recv_count[e] - tokens_per_expert[e] + idx_small[(long long)t * K + lane];
+    if constexpr (TABLES) {
+        int e = -1, s = 0;
+        if (lane < K) {
+            const long long e64 = ld_idx<I32>(topk_idx, (long long)t * K + lane);
+            s = idx_small[(long long)t * K + lane];
+            if (e64 >= 0 && e64 < E) e = (int)e64;
+        }
+        const int32_t base = wave_excl_prefix_at(tokens_per_expert, E, e);
+        if (e >= 0) {
+            const int r = base + s;
             if (r >= 0 && r < row_capacity) r_l = r;
+        }
+    } else {
+        if (lane < K) {
+            const long long e = ld_idx<I32>(topk_idx, (long long)t * K + lane);
+            if (e >= 0 && e < E) {
+                const int r = recv_count[e] - tokens_per_expert[e] + idx_small[(long long)t * K + lane];
+                if (r >= 0 && r < row_capacity) r_l = r;
+            }
         }
     }
     const unsigned long long lmask = __ballot(r_l >= 0);
@@ -1239,9 +1317,44 @@ extern "C" int mi_ep_dispatch_stage_local(const void *x, const void *topk_idx, i
     with_quant_mode<MI_EP_QUANT_NONE, MI_EP_QUANT_MXFP4_E2M1>(quant_mode, [&](auto qm) {
         with_flag(idx_is_i32, [&](auto i32) {
             with_flag(nt_from != 0x7fffffff, [&](auto nt) {
-                stage_local_kernel<i32, qm, nt><<<blocks, kWave * kStageWaves, 0, (hipStream_t)stream>>>(
+                stage_local_kernel<i32, qm, nt, false><<<blocks, kWave * kStageWaves, 0, (hipStream_t)stream>>>(
                     (const uint16_t *)x, topk_idx, send_token_idx_small, recv_count, num_tokens_per_expert, T, K, H, E, (uint8_t *)recv_x,
-                    recv_x_scales, recv_src_idx, rows_hint, nt_from, local_row_out);
+                    recv_x_scales, recv_src_idx, rows_hint, nt_from, local_row_out, LocalTables{});
+            });
+        });
+    });
+    return launch_status();
+}
+
+extern "C" int mi_ep_dispatch_stage_local_tables(const void *x, const void *topk_idx, int idx_is_i32, const int32_t *send_token_idx_small,
+                                                 const int32_t *num_tokens_per_expert, int T, int K, int H, int E, int quant_mode,
+                                                 int rows_hint, void *recv_x, float *recv_x_scales, int32_t *recv_src_idx,
+                                                 int32_t *local_row_out, int relative_pull, int32_t *cnt_matrix, int32_t *recv_count,
+                                                 int32_t *recv_offset, int32_t *recv_tokens_per_expert, int32_t *expert_global_offset,
+                                                 int32_t *srcrank_in_expert_offset, int32_t *r_in_srcrank_offset, int32_t *total_recv_token,
+                                                 int32_t *max_bs, int32_t *pull_offset, int32_t *summary_host, uint64_t *epoch_ctr,
+                                                 void *stream)
+{
+    if (T < 0 || K <= 0 || K > MI_EP_MAX_TOPK || !dispatch_mode_ok(quant_mode, H) || H > MI_EP_MAX_HIDDEN || E <= 0 || E > 2048 ||
+        (quant_is_mx(quant_mode) && !recv_x_scales))
+        return MI_EP_EINVAL;
+    if (!num_tokens_per_expert || !cnt_matrix || !recv_count || !recv_offset || !recv_tokens_per_expert || !expert_global_offset ||
+        !srcrank_in_expert_offset || !r_in_srcrank_offset || !total_recv_token || !max_bs || !pull_offset)
+        return MI_EP_EINVAL;
+    const bool rows = T > 0 && rows_hint > 0;                   // without rows the launch is the tables workgroup alone
+    if (rows && (!x || !topk_idx || !send_token_idx_small || !recv_x || !recv_src_idx)) return MI_EP_EINVAL;
+    const LocalTables tb{cnt_matrix, recv_count, recv_offset, recv_tokens_per_expert, expert_global_offset, srcrank_in_expert_offset,
+                         r_in_srcrank_offset, total_recv_token, max_bs, pull_offset, summary_host, epoch_ctr, relative_pull};
+    const RowPayload pl = row_payload(H, quant_mode);
+    const int blocks = 1 + (rows ? (T + kStageWaves - 1) / kStageWaves : 0);
+    const int nt_from = rows ? pull_nt_from_row(rows_hint, pl.data + pl.scales) : 0x7fffffff;
+    const size_t lds = (size_t)(3 * E + 3) * sizeof(int32_t);    // notify_tables_body's scratch at W = 1 (24.6 KB at E = 2048)
+    with_quant_mode<MI_EP_QUANT_NONE, MI_EP_QUANT_MXFP4_E2M1>(quant_mode, [&](auto qm) {
+        with_flag(idx_is_i32, [&](auto i32) {
+            with_flag(nt_from != 0x7fffffff, [&](auto nt) {
+                stage_local_kernel<i32, qm, nt, true><<<blocks, kWave * kStageWaves, lds, (hipStream_t)stream>>>(
+                    (const uint16_t *)x, topk_idx, send_token_idx_small, nullptr, num_tokens_per_expert, T, K, H, E,
+                    (uint8_t *)recv_x, recv_x_scales, recv_src_idx, rows_hint, nt_from, local_row_out, tb);
             });
         });
     });

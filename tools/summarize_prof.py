@@ -115,8 +115,10 @@ def main():
         # N = 1 with the single-rank dispatch (mi_ep_dispatch_stage_local, the default): the headline's stage + pull_local pair is ONE
         # launch, and pull_local_kernel no longer runs anywhere in bench.py (ep8_proxy pulls by index).  The fused kernel stands in for
         # it; its bytes are recorded under its own name.  (bench.py's headline traffic is the combine_reduce row, unaffected.)
-        stand_in = {"pull_local_kernel<false, true>": "stage_local_kernel<false, 1, true>"}
-        missing = [k for k in wanted if k not in out and stand_in.get(k) not in out]
+        # (stage_local_kernel<..., true>: the one-launch form that also builds the count tables, the default; <..., false> with
+        # MI_EP_DISPATCH_LOCAL_TABLES=0)
+        stand_in = {"pull_local_kernel<false, true>": ("stage_local_kernel<false, 1, true, true>", "stage_local_kernel<false, 1, true, false>")}
+        missing = [k for k in wanted if k not in out and not any(n in out for n in stand_in.get(k, ()))]
         if missing:
             print("PMC counters are missing kernels that bench.py prices:", missing, "-- have:", sorted(out), file=sys.stderr)
             sys.exit(2)
