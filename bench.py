@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Hot-path benchmark: DeepEP normal dispatch (INT8) + combine (BF16) on MI355X, BASELINE.json config C2 shapes.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+A plain run does what the headline figure needs and nothing else: set-up (process group, inputs, buffer, one first step that makes
+the expert stand-in and whose round trip decides which strategy the steps are timed on: the default one, or the alltoall fallback
+when it fails), W warm-up steps, K timed steps, the --dump-outputs files, the JSON line.  Everything
+else described below -- the second, event-timed pass behind `roofline` / `kernels`, `no_host_sync`, `ep8_proxy`, `xgmi_projection`,
+`xgmi`, `low_latency`, `fused_deep_moe`, `mla_decode`, `cpu_baseline` -- is measured only with --full (`extra_sections`), after the
+timed steps, so the headline of a --full run is taken exactly as a plain run takes it.
 
 One step = one pass of the hot path over one batch of synthetic tokens on every rank:
     get_dispatch_layout -> dispatch(quant_mode="int8") -> combine(BF16)          (deep_ep.Buffer API, EP = N ranks)
@@ -12,11 +19,11 @@ Weak scaling: per-GPU work is fixed as N grows.
 `value` follows the reference's own bandwidth convention (tests/python/deepep/test_intranode.py:447-448,530-534):
 bytes = BF16-equivalent size of every received row (local rows included) for dispatch plus the same for combine,
 summed over all ranks, divided by the max-over-ranks step time.  At N = 1 everything is a local permutation and the
-kernels are HBM-bound; the `roofline` object prices the dominant kernel against HBM.  At N > 1 both dispatch transports
+kernels are HBM-bound; with --full the `roofline` object prices the dominant kernel against HBM.  At N > 1 both dispatch transports
 (push = remote writes, pull = remote reads) are timed with the same K steps; the faster one is the headline, the other is
-reported beside it under `transports`, and `xgmi` prices the cross-GPU legs against 153 GB/s per link.
+reported beside it under `transports`, and with --full `xgmi` prices the cross-GPU legs against 153 GB/s per link.
 
-Further objects on the same JSON line (the other BASELINE configs, measured by the same process):
+Further objects on the JSON line of a --full run (the other BASELINE configs, measured by the same process):
   low_latency     C3: low-latency dispatch / combine at 128 tokens per rank, p50 / p99 per call (HIP events)
   fused_deep_moe  C5: dispatch -> INT8 grouped GEMM1 + SwiGLU -> requant -> GEMM2 -> combine, 4096 tokens per rank, 32 local experts
   mla_decode      C4: MLA paged decode (N = 1 only) with its own roofline and cpu_baseline
@@ -52,9 +59,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--tokens", type=int, default=T_TOKENS)
     ap.add_argument("--strategy", default=os.getenv("DEEP_BENCH_STRATEGY", "default"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-mla", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3 (low-latency) and C5 (fused_deep_moe) sections")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the event-timed pass (roofline, kernels, "
+                         "xgmi), no_host_sync, ep8_proxy, xgmi_projection, C3 (low_latency), C5 (fused_deep_moe), C4 (mla_decode) and "
+                         "the CPU baselines; off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-mla", action="store_true", help="with --full: skip the C4 (mla_decode) section")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the C3 (low_latency) and C5 (fused_deep_moe) sections")
     ap.add_argument("--dry-run-8", action="store_true",
                     help="plumbing check of the 8-GPU launch on ONE GPU: re-executes itself as 8 ranks that all use cuda:0 (gloo bootstrap, "
                          "hipIpc windows), full C2 size; the JSON line carries every N > 1 key and \"dry_run_single_device\": true -- NOT a measurement")
@@ -84,13 +95,30 @@ def self_launch_command(args, environ):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(29600 + os.getpid() % 300), os.path.abspath(__file__), "--gpus", str(n), "--steps", str(args.steps),
            "--warmup", str(args.warmup), "--tokens", str(args.tokens), "--strategy", args.strategy]
-    for flag, on in (("--dry-run-8", args.dry_run_8), ("--no-extra", args.no_extra), ("--no-mla", args.no_mla),
+    for flag, on in (("--dry-run-8", args.dry_run_8), ("--full", args.full), ("--no-extra", args.no_extra), ("--no-mla", args.no_mla),
                      ("--no-cpu-baseline", args.no_cpu_baseline)):
         if on:
             cmd.append(flag)
     if args.dump_outputs:
         cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     return cmd, env
+
+
+def extra_sections(args, world, windowed):
+    """What this run measures beside the headline, as a set of names: nothing without --full.  `windowed`: the buffer runs the
+    window strategy with the runtime's profile hooks (the event-timed pass, no_host_sync, ep8_proxy, C3 and C5 need it)."""
+    if not args.full:
+        return frozenset()
+    s = set()
+    if windowed:
+        s |= {"profiled_pass", "no_host_sync", "ep8_proxy"}
+        if not args.no_extra:
+            s |= {"low_latency", "fused_deep_moe"}
+    if world == 1 and not args.no_mla:
+        s.add("mla_decode")
+    if world == 1 and not args.no_cpu_baseline:
+        s.add("cpu_baseline")
+    return frozenset(s)
 
 
 def init_dist(n):
@@ -829,6 +857,7 @@ def main():
         validated = check_round_trip(out, x, topk_w) < 3e-3
     strategy = buf.normal_strategy.get_name()
     windowed = strategy == "default" and hasattr(buf.runtime, "get_profile_summary")
+    sections = extra_sections(args, world, windowed)
 
     # ---- the timed region(s): exactly K steps per transport, barrier + synchronize on both sides, max over ranks
     transports = [None]
@@ -839,12 +868,12 @@ def main():
         if tr is not None:
             buf.runtime.set_dispatch_transport(tr)
         keep = (lambda step, tr=tr: last_outputs.update({tr: step_outputs(step, rank, world)})) if args.dump_outputs else None
-        # the timed region: exactly K steps, no instrumentation.  Kernel durations (roofline) come from a SECOND pass of the same
-        # K steps with a HIP event pair around every kernel: each pair costs ~10 us of bubble at a kernel boundary (0.396 -> 0.448 ms
-        # per step measured), which must not be charged to the hot path; that pass's own time is reported as profiled_ms_per_step.
+        # the timed region: exactly K steps, no instrumentation.  With --full, kernel durations (roofline) come from a SECOND pass of
+        # the same K steps with a HIP event pair around every kernel: each pair costs ~10 us of bubble at a kernel boundary (0.396 ->
+        # 0.448 ms per step measured), which must not be charged to the hot path; that pass's own time is reported as profiled_ms_per_step.
         dt, _, err = timed_steps(buf, x, topk_idx, topk_w, y, args.steps, args.warmup, False, on_last=keep)
         prof, dt_prof = {}, None
-        if err is None and windowed:
+        if err is None and "profiled_pass" in sections:
             dt_prof, prof, err = timed_steps(buf, x, topk_idx, topk_w, y, args.steps, 0, True)
         if err is None:
             runs[tr] = (dt, prof, dt_prof)
@@ -867,7 +896,7 @@ def main():
     # ---- the same K steps without the host on the critical path (dispatch(num_worst_tokens = T * K * W): worst-case sized outputs, the
     # host never reads the receive count): what a serving stack that captures the step in a graph pays
     nosync = None
-    if windowed:
+    if "no_host_sync" in sections:
         try:
             worst = T * TOPK * world
             out_ns, y_ns = one_step_nosync(buf, x, topk_idx, topk_w, None, worst)
@@ -902,7 +931,7 @@ def main():
     # pull_indexed / stage_push for all rows; combine: every row pushed through the window), which is what 7/8 of the rows of an EP = 8
     # rank do.  Same results; the kernel times transfer to EP = 8 as HBM-side costs (the xGMI legs come on top).
     proxy = None
-    if windowed and hasattr(buf.runtime, "set_local_row_paths"):
+    if "ep8_proxy" in sections and hasattr(buf.runtime, "set_local_row_paths"):
         was = list(buf.runtime.get_local_row_paths())
         buf.runtime.set_local_row_paths(False, False)
         try:
@@ -914,12 +943,12 @@ def main():
 
     # ---- the other BASELINE configs, same process group (every rank takes part)
     extra = {}
-    if windowed and not args.no_extra:
-        for name, fn in (("low_latency", low_latency_section), ("fused_deep_moe", fused_moe_section)):
+    for name, fn in (("low_latency", low_latency_section), ("fused_deep_moe", fused_moe_section)):
+        if name in sections:
             extra[name] = fn(buf, rank, world)
 
     pairs_to, tokens_to = routing_stats(topk_idx, world, rank)
-    rows_from = torch.bincount(handle[3][:3 * n_recv].view(-1, 3)[:, 0].long(), minlength=world).tolist() if windowed else [0] * world
+    rows_from = torch.bincount(handle[3][:3 * n_recv].view(-1, 3)[:, 0].long(), minlength=world).tolist() if "profiled_pass" in sections else [0] * world
     if rank != 0:
         dist.destroy_process_group()
         flush_c_stdout()
@@ -936,9 +965,10 @@ def main():
                                f"top-{TOPK} of {EXPERTS} experts (BASELINE C2 shapes at EP={world})",
                    "strategy": strategy, "dispatch_transport": best, "tokens_per_rank": T, "hidden": HIDDEN, "topk": TOPK,
                    "experts": EXPERTS, "cache_flush": "256 MB write before the timed region"},
-        "per_gpu_GBps": value / world, "validated_round_trip": bool(validated),
-        "profiled_ms_per_step": dt_prof / args.steps * 1e3 if dt_prof else None,     # second pass of K steps with HIP events (roofline)
+        "per_gpu_GBps": value / world, "validated_round_trip": bool(validated), "full": args.full,
     }
+    if args.full:
+        result["profiled_ms_per_step"] = dt_prof / args.steps * 1e3 if dt_prof else None     # second pass of K steps with HIP events (roofline)
     if len(runs) > 1:
         result["transports"] = {k: {"ms_per_step": v[0] / args.steps * 1e3, "value": bytes_per_step / (v[0] / args.steps) / 1e9}
                                 for k, v in runs.items()}
@@ -992,11 +1022,11 @@ def main():
     if args.dry_run_8:
         result["dry_run_single_device"] = True       # every rank ran on cuda:0: plumbing only, not a measurement
     result.update(extra)
-    if world == 1 and not args.no_mla:          # before the CPU leg: the GPU clocks sag while the host works alone
+    if "mla_decode" in sections:                # before the CPU leg: the GPU clocks sag while the host works alone
         mla = mla_section(args)
         if mla is not None:
             result["mla_decode"] = mla
-    if world == 1 and not args.no_cpu_baseline:
+    if "cpu_baseline" in sections:
         result["cpu_baseline"] = cpu_baseline(T)
     # The JSON line must be the last thing on stdout.  RCCL printf()s its version banner at communicator creation; with stdout
     # a pipe that text waits in libc's buffer until exit -- i.e. after anything Python prints -- unless it is flushed first.

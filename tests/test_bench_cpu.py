@@ -1,4 +1,5 @@
-"""bench.py host logic that needs no GPU: the self-launch decision for --gpus N > 1 and the xGMI projection arithmetic."""
+"""bench.py host logic that needs no GPU: the self-launch decision for --gpus N > 1, what a plain and a --full run measure beside the
+headline, and the xGMI projection arithmetic."""
 import argparse
 import importlib.util
 import os
@@ -18,7 +19,7 @@ def _bench():
 
 def _args(**kw):
     d = dict(gpus=1, steps=30, warmup=5, tokens=4096, strategy="default", no_cpu_baseline=False, no_mla=False, no_extra=False,
-             dry_run_8=False, dump_outputs=None)
+             dry_run_8=False, dump_outputs=None, full=False)
     d.update(kw)
     return argparse.Namespace(**d)
 
@@ -35,6 +36,7 @@ def test_self_launch_decision():
     assert cmd[cmd.index("--nproc-per-node") + 1] == "8" and cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     tail = cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:]
     assert tail[:6] == ["--gpus", "8", "--steps", "7", "--warmup", "2"] and "--no-extra" in tail and "--dry-run-8" not in tail
+    assert "--full" not in tail
     assert env["HSA_ENABLE_IPC_MODE_LEGACY"] == "0" and "BENCH_SINGLE_DEVICE" not in env and env["PATH"] == "/usr/bin"
     cmd, env = B.self_launch_command(_args(gpus=2), {})
     assert cmd[cmd.index("--nproc-per-node") + 1] == "2" and cmd[cmd.index("--gpus") + 1] == "2" and "--dump-outputs" not in cmd
@@ -42,15 +44,40 @@ def test_self_launch_decision():
     assert cmd[cmd.index("--dump-outputs") + 1] == os.path.abspath("out")
     # --dry-run-8: the same re-execution with every rank on cuda:0
     cmd, env = B.self_launch_command(_args(dry_run_8=True), {})
-    assert env["BENCH_SINGLE_DEVICE"] == "1" and "--dry-run-8" in cmd and cmd[cmd.index("--gpus") + 1] == "8"
+    assert env["BENCH_SINGLE_DEVICE"] == "1" and "--dry-run-8" in cmd and cmd[cmd.index("--gpus") + 1] == "8" and "--full" not in cmd
+    # --full reaches the re-executed ranks
+    cmd, env = B.self_launch_command(_args(gpus=2, full=True), {})
+    assert "--full" in cmd
+    saved = sys.argv
+    try:
+        sys.argv = ["bench.py"] + cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:]
+        assert B.parse().full is True
+    finally:
+        sys.argv = saved
     # the re-executed ranks parse what the parent passed
     sys_argv = sys.argv
     try:
         sys.argv = ["bench.py"] + tail
         a = B.parse()
-        assert a.gpus == 8 and a.steps == 7 and a.warmup == 2 and a.no_extra and a.dump_outputs is None
+        assert a.gpus == 8 and a.steps == 7 and a.warmup == 2 and a.no_extra and a.dump_outputs is None and a.full is False
     finally:
         sys.argv = sys_argv
+
+
+def test_plain_run_measures_the_headline_alone():
+    """Without --full nothing is measured beside the headline, whatever else is on the command line; --full brings back every section,
+    each still subject to its own --no-* switch, the size of the job and the strategy in use."""
+    B = _bench()
+    for kw in ({}, dict(gpus=8), dict(dry_run_8=True), dict(no_mla=True, no_extra=True, no_cpu_baseline=True), dict(dump_outputs="d")):
+        for world in (1, 8):
+            for windowed in (False, True):
+                assert B.extra_sections(_args(**kw), world, windowed) == frozenset()
+    everything = {"profiled_pass", "no_host_sync", "ep8_proxy", "low_latency", "fused_deep_moe", "mla_decode", "cpu_baseline"}
+    assert B.extra_sections(_args(full=True), 1, True) == everything
+    assert B.extra_sections(_args(full=True, gpus=8), 8, True) == everything - {"mla_decode", "cpu_baseline"}
+    assert B.extra_sections(_args(full=True, no_extra=True), 1, True) == everything - {"low_latency", "fused_deep_moe"}
+    assert B.extra_sections(_args(full=True, no_mla=True, no_cpu_baseline=True), 1, True) == everything - {"mla_decode", "cpu_baseline"}
+    assert B.extra_sections(_args(full=True), 1, False) == {"mla_decode", "cpu_baseline"}      # the alltoall fallback has no profile hooks
 
 
 def test_step_count_is_validated(monkeypatch, capsys):

@@ -6,6 +6,6 @@ for l in sys.stdin:
 cp sgl-kernel-npu_amd/lib/libmi_ep.so /tmp/libmi_ep_orig.so
 for v in "$@"; do
   cp sgl-kernel-npu_amd/lib/libmi_ep_$v.so sgl-kernel-npu_amd/lib/libmi_ep.so
-  python bench.py --steps 100 --warmup 100 2>/dev/null | python -c "$P" $v
+  python bench.py --full --steps 100 --warmup 100 2>/dev/null | python -c "$P" $v
 done
 cp /tmp/libmi_ep_orig.so sgl-kernel-npu_amd/lib/libmi_ep.so

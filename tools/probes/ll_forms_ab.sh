@@ -7,6 +7,6 @@ for l in sys.stdin:
 for rep in 1 2; do
   for v in ${FORMS:-"0 0" "2 2"}; do
     set -- $v
-    MI_EP_LL_FUSED_COUNTS=$1 MI_EP_COMBINE_FUSED=$2 python bench.py --no-mla --no-cpu-baseline 2>/dev/null | python -c "$P" dispatch_$1_combine_$2
+    MI_EP_LL_FUSED_COUNTS=$1 MI_EP_COMBINE_FUSED=$2 python bench.py --full --no-mla --no-cpu-baseline 2>/dev/null | python -c "$P" dispatch_$1_combine_$2
   done
 done
