@@ -172,28 +172,14 @@ int mi_ep_notify_post(uint64_t *const *peer_notify_host, int num_ranks, int my_r
                       const int32_t *num_tokens_per_expert, int num_tokens, uint32_t epoch, void *stream);
 int mi_ep_notify_wait(const uint64_t *my_notify, int num_ranks, int num_experts, uint32_t epoch,
                       int32_t *cnt_matrix, int32_t *status, int timeout_ms, void *stream);
-/* Fused forms used by the one-process-per-GPU runtime (fewer launches on the critical path):
- * notify_post_signal = mi_ep_notify_post + mi_ep_signal(peer_flags, signal_epoch);
- * notify_wait_tables = mi_ep_notify_wait + mi_ep_wait(my_flags, flag_epoch; skipped when my_flags is NULL) +
- *                      mi_ep_notify_tables, one workgroup. */
-int mi_ep_notify_post_signal(uint64_t *const *peer_notify_host, uint64_t *const *peer_flags_host, int num_ranks, int my_rank,
-                             int num_experts, const int32_t *num_tokens_per_expert, int num_tokens, uint32_t notify_epoch,
-                             uint64_t signal_epoch, void *stream);
-int mi_ep_notify_wait_tables(const uint64_t *my_notify, uint32_t notify_epoch, const uint64_t *my_flags, uint64_t flag_epoch,
-                             int32_t *cnt_matrix, int num_ranks, int num_experts, int my_rank, int relative_pull,
-                             int32_t *recv_count, int32_t *recv_offset, int32_t *recv_tokens_per_expert,
-                             int32_t *expert_global_offset, int32_t *srcrank_in_expert_offset, int32_t *r_in_srcrank_offset,
-                             int32_t *total_recv_token, int32_t *max_bs, int32_t *pull_offset, int32_t *summary_host,
-                             int32_t *status, int timeout_ms, int32_t *wait_cost_stats /*[W] or NULL: += us waited per source*/,
-                             void *stream);
-/* Dynamic LDS of the notify_wait_tables / notify_exchange_tables workgroup for (num_ranks, num_experts): it keeps the W * (E + 1)
- * counts next to the tables' scratch.  Shapes needing more than a CU's 160 KB (0 = invalid W / E) make those two entry points
+/* Dynamic LDS of the mi_ep_notify_exchange_tables workgroup for (num_ranks, num_experts): it keeps the W * (E + 1)
+ * counts next to the tables' scratch.  Shapes needing more than a CU's 160 KB (0 = invalid W / E) make that entry point
  * return MI_EP_EINVAL -- e.g. W = 64 with E = 2048; every shape with W <= 16 fits up to E = 2048, W = 64 up to E = 512. */
 size_t mi_ep_notify_lds_bytes(int num_ranks, int num_experts);
 /* Both halves of the exchange in ONE launch of one workgroup: post this rank's counts and its "rows staged" flag
- * (= mi_ep_notify_post_signal with signal_epoch = flag_epoch), then mi_ep_notify_wait_tables.  Used by the host runtime
- * when each rank is its own process; a harness that plays several ranks on one stream must keep the two halves apart
- * (every rank has to post before any rank can finish waiting). */
+ * (= mi_ep_notify_post + mi_ep_signal(peer_flags, flag_epoch)), then collect and derive (= mi_ep_notify_wait +
+ * mi_ep_wait(my_flags, flag_epoch) + mi_ep_notify_tables).  Used by the host runtime when each rank is its own
+ * process; a harness that plays several ranks on one stream must keep the two halves apart (every rank has to post before any rank can finish waiting). */
 int mi_ep_notify_exchange_tables(uint64_t *const *peer_notify_host, uint64_t *const *peer_flags_host,
                                  const int32_t *num_tokens_per_expert, int num_tokens, const uint64_t *my_notify,
                                  uint32_t notify_epoch, const uint64_t *my_flags, uint64_t flag_epoch, int32_t *cnt_matrix,
@@ -340,15 +326,6 @@ int mi_ep_dispatch_stage_push(const void *x, const void *topk_idx, int idx_is_i3
 int mi_ep_combine_push(const void *x, const int32_t *src_idx, const int32_t *total_rows_dev, int rows_hint,
                        int hidden, int num_topk, void *const *dst_base_host, int num_ranks, size_t slot_region_bytes,
                        const uint64_t *epoch_ctr, size_t parity_stride, int my_rank, int32_t *local_row, void *stream);
-/* push + "my rows are pushed" + the wait for every expert rank in ONE launch (mi_ep_combine_push followed by mi_ep_signal_wait with
- * epoch_ctr): every workgroup writes its rows through the caches, drains and counts itself in at *arrive_word (a device word of the
- * rank's own control area: zero before the first call; the kernel re-arms it); the last workgroup to arrive raises this rank's flag at
- * every owner, waits (bounded by timeout_ms, reported through *status) for every expert rank's and completes the family's call counter.
- * Same bytes in the same slots.  One call in flight per arrive_word. */
-int mi_ep_combine_push_signal_wait(const void *x, const int32_t *src_idx, const int32_t *total_rows_dev, int rows_hint, int hidden, int num_topk,
-                                   void *const *dst_base_host, int num_ranks, size_t slot_region_bytes, uint64_t *epoch_ctr,
-                                   size_t parity_stride, int my_rank, int32_t *local_row, uint64_t *const *peer_flags_host,
-                                   const uint64_t *my_flags, uint32_t *arrive_word, int32_t *status, int timeout_ms, void *stream);
 /* The TWO-launch combine (the reference waits per token for the rows it sums, moe_distribute_combine_v2.h:952-1002): mi_ep_combine_push_flagged =
  * mi_ep_combine_push whose waves write their rows through the caches and, once a row's stores have drained, raise the row's flag word at
  * its owner -- uint32 [2 halves, row_flags_parity_stride bytes apart][slot rows] in every rank's control area, word t * K + k of the half
@@ -424,25 +401,12 @@ int mi_ep_ll_dispatch_recv(const void *my_rows, const uint64_t *my_counts, uint3
                            void *packed_recv_x, float *packed_recv_x_scales, int64_t *packed_recv_count,
                            int32_t *src_info, int32_t *layout_range, int rows_capacity /* rows packed_recv_x holds; 0 = L*W*max_tokens */,
                            int32_t *status, int timeout_ms, void *stream);
-/* Layout + send + the count exchange in ONE launch, then the packing launch: two launches per low-latency dispatch instead of three.
- * mi_ep_ll_dispatch_layout_send_counts = mi_ep_ll_dispatch_layout_send whose workgroups count themselves in at *arrive_word (a device
- * word of the rank's own control area: zero before the first call; the kernel re-arms it) once their rows -- written through the caches
- * -- have drained; the last one to arrive posts this rank's per-expert counts, collects everybody's (bounded by timeout_ms, reported
- * through *status), leaves the cumulative counts in layout_range [L*W] and packed_recv_count [L], and completes the family's call
- * counter (epoch_ctr: required).  mi_ep_ll_pack = the packing half of mi_ep_ll_post_recv.  Same rows, tables and bytes. */
-int mi_ep_ll_dispatch_layout_send_counts(const void *x, const void *topk_idx, int idx_is_i32, int num_tokens, int num_topk, int hidden,
-                                         int num_experts, int num_ranks, int my_rank, int max_tokens, int quant_mode, void *const *peer_rows_host,
-                                         uint64_t *epoch_ctr, size_t parity_stride, int32_t *num_tokens_per_rank,
-                                         int32_t *num_tokens_per_expert, int32_t *is_token_in_rank, int32_t *send_token_idx_small,
-                                         int32_t *send_data_offset, uint64_t *const *peer_counts_host, const uint64_t *my_counts,
-                                         size_t counts_parity_stride, int count_type, int32_t *layout_range, int64_t *packed_recv_count,
-                                         uint32_t *arrive_word, int32_t *status, int timeout_ms, void *stream);
 /* The TWO-launch low-latency dispatch with nothing between the launches.  mi_ep_ll_dispatch_layout_send_tagged = mi_ep_ll_dispatch_layout_send
  * whose layout workgroup posts this rank's per-expert counts to every peer's count granules as soon as it has them (half (*epoch_ctr + 1) & 1,
  * granule = epoch << 32 | count) and leaves the call's epoch at *cur_epoch_word (own control area), and whose send waves write every row's
  * payload through the caches, drain, and only then its meta -- word 3 = src_rank | tag << 8, tag = epoch % 0xFFFFFF + 1: nobody waits in this
- * launch.  mi_ep_ll_wait_pack = the count exchange's collecting half + mi_ep_ll_pack in one launch of <= 512 workgroups: each collects the L * W
- * granules of the epoch at *cur_epoch_word (bounded by timeout_ms; code 2000 + i through *status), scans them, and packs its rows, waiting
+ * launch.  mi_ep_ll_wait_pack = the collecting half of the count exchange + the packing half of mi_ep_ll_post_recv in one launch of <= 512
+ * workgroups: each collects the L * W granules of the epoch at *cur_epoch_word (bounded by timeout_ms; code 2000 + i through *status), scans them, and packs its rows, waiting
  * per row for the tag (code 2500 + ..); workgroup 0 writes layout_range / packed_recv_count and completes *epoch_ctr.  Same rows, tables and
  * bytes as the three-launch form (src_info word 0 = the meta word's low 8 bits).  Reference: per-token arrival state instead of a global
  * barrier, moe_distribute_dispatch_v2.h:1477-1490. */
@@ -456,9 +420,6 @@ int mi_ep_ll_wait_pack(const void *my_rows, const uint64_t *my_counts, size_t co
                        int max_tokens, int hidden, int quant_mode, int count_type, void *packed_recv_x, float *packed_recv_x_scales,
                        int64_t *packed_recv_count, int32_t *src_info, int32_t *layout_range, int rows_capacity, const uint64_t *cur_epoch_word,
                        uint64_t *epoch_ctr, size_t rows_parity_stride, int32_t *status, int timeout_ms, int max_blocks, void *stream);
-int mi_ep_ll_pack(const void *my_rows, const int32_t *layout_range, int num_ranks, int num_local_experts, int max_tokens, int hidden,
-                  int quant_mode, void *packed_recv_x, float *packed_recv_x_scales, int32_t *src_info, int rows_capacity,
-                  const uint64_t *epoch_ctr, size_t rows_parity_stride, void *stream);
 /* ll_post_counts fused into the receive (one rank per process): the counts workgroup posts this rank's counts, collects
  * everybody's, scans them; the packing kernel follows.  Two launches instead of three. */
 int mi_ep_ll_post_recv(uint64_t *const *peer_counts_host, const int32_t *num_tokens_per_expert, int my_rank, const void *my_rows,

@@ -81,7 +81,7 @@ public:
     bool self_test_in_launch(int64_t test_timeout_ms, int64_t skip_payload_from_round);
     void set_two_launch_forms(bool ok) { two_launch_forms_ok = ok; }
     bool get_two_launch_forms() const { return two_launch_forms_ok; }
-    // the forms of a dispatch and of a combine behind a dispatch (0 three launches, 1 tail-fused, 2 two launches) ...
+    // the forms of a dispatch and of a combine behind a dispatch (0 three launches, 2 two launches) ...
     std::vector<int64_t> get_low_latency_default_forms() const
     {
         return {ll_launch_form("MI_EP_LL_FUSED_COUNTS"), ll_launch_form("MI_EP_COMBINE_FUSED")};
@@ -293,12 +293,11 @@ private:
                        at::Tensor &rx, at::Tensor &rs, at::Tensor &src_idx, hipStream_t st);
     at::Tensor combine_finish(const at::Tensor &topk_idx, const float *topk_weights, int H, int E, const at::TensorOptions &opts,
                               const char *reduce_name, hipStream_t st, const at::Tensor &x_local = at::Tensor(),
-                              const at::Tensor &local_row = at::Tensor(), int signalled = 0);
-    // push + signal + wait in one launch (mi_ep_combine_push_signal_wait); MI_EP_COMBINE_FUSED=0: the separate signal_wait launch
+                              const at::Tensor &local_row = at::Tensor(), bool rows_flagged = false);
+    // the push of a combine; rows_flagged comes back true when the rows carry flags (mi_ep_combine_push_flagged: combine_finish then runs the
+    // flagged reduce), and stays false when the plain push ran (combine_finish: the separate signal_wait launch, then the reduce)
     void combine_push_rows(const at::Tensor &x, const int32_t *src_idx, const int32_t *total_rows_dev, int rows_hint, int H, int K,
-                           const at::Tensor &local_row, const char *name, hipStream_t st, int &signalled, bool may_flag_rows = false);
-    uint32_t *arrive_word();
-    uint64_t arrive_calls = 0;
+                           const at::Tensor &local_row, const char *name, hipStream_t st, bool &rows_flagged, bool may_flag_rows = false);
     bool ranks_share_device = false;
     bool two_launch_forms_ok = true;       // cleared when the in-launch self-test leg failed on any rank
     // A two-launch combine is only safe behind a dispatch: its reduce waits for the ranks that serve ITS tokens, not for everybody, so with
@@ -307,8 +306,8 @@ private:
     // three-launch form (whose signal / wait is all-to-all).  Every rank makes the same calls, so every rank switches together.
     bool last_ll_call_was_combine = false;
     uint64_t last_ll_dispatch_capture = 0;      // graph capture the last low_latency_dispatch was recorded into (0: it ran eagerly)
-    // launch form of the low-latency dispatch / combine: the env value if set, else 2 (two launches, nothing between them) when every rank owns
-    // its GPU and 0 (three launches) when ranks share one
+    // launch form of the low-latency dispatch / combine, 2 (two launches, nothing between them) or 0 (three launches): 2 where the env asks
+    // for 2, or is unset and every rank owns its GPU, and the in-launch self-test passed; 0 otherwise (any other env value, ranks sharing a GPU)
     int ll_launch_form(const char *env_name) const;
     at::Tensor combine_local_rows(const at::Tensor &topk_idx) const;
     struct LocalRowEntry {

@@ -21,34 +21,25 @@ namespace mi_ep {
 
 constexpr int kPushWaves = 4;
 
-// "My rows are pushed" raised from INSIDE the push launch (TAIL): every workgroup writes its rows through (sc0 sc1), drains, and counts
-// itself in at a device word of the rank's control area; the last one to arrive does what signal_wait_kernel does in a launch of its
-// own -- raise this rank's flag at every owner, wait (bounded) for every expert rank's, complete the family's call counter -- and
-// re-arms the word.  One launch and one kernel boundary less per combine (low-latency: three launches -> two).
-struct PushTail {
-    uint32_t *arrive;             // zero between calls (control area: zeroed at creation, re-armed by the last arriver)
-    PeerPtrs flag_peers;          // every rank's combine flag group
-    const uint64_t *my_flags;
-    uint64_t *epoch_bump;         // the family's completed-call counter (also this call's epoch source: counter + 1)
-    int32_t *status;
-    uint64_t timeout_ticks;
-    // FLAGGED form (arrive == NULL, row_flag_peers set): no tail at all -- every wave raises the flag word of ITS row at the row's owner once
-    // the row's write-through stores have drained (the reference's per-token arrival state, moe_distribute_combine_v2.h:952-1002); the
-    // owner's reduce waits per selection (combine_reduce_kernel<.., FLAGGED>).  Words are tagged with the call's epoch, never cleared.
+// FLAGGED push (the two-launch combine, mi_ep_combine_push_flagged): every wave raises the flag word of ITS row at the row's owner once the
+// row's write-through stores have drained (the reference's per-token arrival state, moe_distribute_combine_v2.h:952-1002); the owner's
+// reduce waits per selection (combine_reduce_kernel<.., FLAGGED>).  Words are tagged with the call's epoch, never cleared.
+struct PushFlags {
+    const uint64_t *epoch_bump;   // the family's completed-call counter (this call's epoch: counter + 1)
     PeerPtrs row_flag_peers;      // every rank's row-flag area: uint32 [2 halves][slot rows]
     size_t row_flags_parity_stride;
-    uint64_t *cur_epoch;          // FLAGGED: the push leaves this call's epoch here for the reduce (which then completes the call counter)
+    uint64_t *cur_epoch;          // the push leaves this call's epoch here for the reduce (which then completes the call counter)
 };
 
-template <bool TAIL>
+template <bool FLAGGED>
 __global__ __launch_bounds__(kWave * kPushWaves) void combine_push_kernel(
     const uint8_t *__restrict__ x, const int32_t *__restrict__ src_idx, const int32_t *__restrict__ total_dev,
     int rows_hint, int row_bytes /*2H*/, size_t slot_stride, int K, int W, PeerPtrs dsts, Parity par, int slot_rows, int my_rank,
-    int32_t *__restrict__ local_row, unsigned deal_stride, PushTail tail)
+    int32_t *__restrict__ local_row, unsigned deal_stride, PushFlags flags)
 {
     // never trust the device-side count beyond the rows the caller's tensor holds
     const int total = total_dev ? min(*total_dev, rows_hint) : rows_hint;
-    if (TAIL && tail.cur_epoch && blockIdx.x == 0 && threadIdx.x == 0) *tail.cur_epoch = *tail.epoch_bump + 1ull;
+    if (FLAGGED && blockIdx.x == 0 && threadIdx.x == 0) *flags.cur_epoch = *flags.epoch_bump + 1ull;
     const size_t poff = parity_off(par);
     const int lane = lane_id();
     const int wave = threadIdx.x / kWave;
@@ -83,50 +74,17 @@ __global__ __launch_bounds__(kWave * kPushWaves) void combine_push_kernel(
             // straight-line groups of whole 1 KB pieces (copy_row, ep_common.h): loads back to back, then the (possibly remote) stores.
             // (nontemporal stores were measured: the push slows 159 -> 183 us, the reduce that follows speeds up 137 -> 122 us because
             //  fewer dirty lines are left behind -- a wash for the step)
-            if (TAIL) copy_row_wt<true>(s16, d16, n16, lane);
+            if (FLAGGED) copy_row_wt<true>(s16, d16, n16, lane);
             else copy_row<true, false>(s16, d16, n16, lane);
-            if (TAIL && !tail.arrive) {
-                // FLAGGED: the row is at its owner (write-through stores, drained) before its flag says so
+            if (FLAGGED) {
+                // the row is at its owner (write-through stores, drained) before its flag says so
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (lane == 0) {
-                    const uint64_t ep64 = *tail.epoch_bump + 1ull;
-                    uint32_t *fl = (uint32_t *)((uint8_t *)tail.row_flag_peers.p[src] + (size_t)(ep64 & 1ull) * tail.row_flags_parity_stride) +
+                    const uint64_t ep64 = *flags.epoch_bump + 1ull;
+                    uint32_t *fl = (uint32_t *)((uint8_t *)flags.row_flag_peers.p[src] + (size_t)(ep64 & 1ull) * flags.row_flags_parity_stride) +
                                    ((size_t)t * K + k);
                     __hip_atomic_store(fl, (uint32_t)ep64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
-            }
-        }
-    }
-    if (TAIL && tail.arrive) {
-        __shared__ uint32_t last_s;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // every wave: its write-through stores are performed
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            // (the local_row words, plain stores read by the NEXT launch, need nothing: the kernel boundary publishes them)
-            const uint32_t old = __hip_atomic_fetch_add(tail.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last_s = old == gridDim.x - 1 ? 1u : 0u;
-        }
-        __syncthreads();
-        if (last_s == 0) return;
-        // the last workgroup: everybody's rows are out.  One wave: signal + wait (signal_wait_kernel, sync.hip), then re-arm.
-        if (threadIdx.x < kWave) {
-            const int s = threadIdx.x;
-            const uint64_t epoch = *tail.epoch_bump + 1ull;
-            if (s < W) {
-                sys_store_u64((uint64_t *)tail.flag_peers.p[s] + my_rank, epoch);
-                const uint64_t t0 = ticks_100mhz();
-                while (sys_load_u64(tail.my_flags + s) < epoch) {
-                    __builtin_amdgcn_s_sleep(8);
-                    if (ticks_100mhz() - t0 > tail.timeout_ticks) {
-                        report_status(tail.status, 1 + s);
-                        break;
-                    }
-                }
-            }
-            // one wave: every lane has read the counter before lane 0 moves it (wave-level program order)
-            if (s == 0) {
-                *tail.epoch_bump = epoch;
-                __hip_atomic_store(tail.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     }
@@ -366,12 +324,12 @@ extern "C" size_t mi_ep_combine_row_bytes(int hidden) { return ((size_t)hidden *
 
 static int combine_push_launch(const void *x, const int32_t *src_idx, const int32_t *total_rows_dev, int rows_hint, int H, int K,
                                void *const *dst_base_host, int W, size_t slot_region_bytes, const uint64_t *epoch_ctr, size_t parity_stride,
-                               int my_rank, int32_t *local_row, const PushTail *tail, void *stream)
+                               int my_rank, int32_t *local_row, const PushFlags *flags, void *stream)
 {
     if (H <= 0 || H % 8 || K <= 0 || K > MI_EP_MAX_TOPK || W <= 0 || W > MI_EP_MAX_RANKS || !dst_base_host ||
         (local_row && (my_rank < 0 || my_rank >= W)))
         return MI_EP_EINVAL;
-    if (rows_hint <= 0 && !tail) return MI_EP_OK;
+    if (rows_hint <= 0 && !flags) return MI_EP_OK;
     if (rows_hint > 0 && (!x || !src_idx)) return MI_EP_EINVAL;
     PeerPtrs pp;
     if (!peer_ptrs(dst_base_host, W, pp)) return MI_EP_EINVAL;
@@ -383,14 +341,14 @@ static int combine_push_launch(const void *x, const int32_t *src_idx, const int3
     unsigned deal_stride = stride_env > 0 ? (unsigned)stride_env | 1u : (W > 1 ? 257u : 1u);
     const Parity par = make_parity(epoch_ctr, 1, parity_stride);
     const int slot_rows = slot_region_bytes ? (int)std::min<size_t>(slot_region_bytes / mi_ep_combine_row_bytes(H), 0x7FFFFFFF) : 0x7FFFFFFF;
-    if (tail)
+    if (flags)
         combine_push_kernel<true><<<(int)blocks, kWave * kPushWaves, 0, (hipStream_t)stream>>>(
             (const uint8_t *)x, src_idx, total_rows_dev, std::max(rows_hint, 0), H * 2, mi_ep_combine_row_bytes(H), K, W, pp, par, slot_rows, my_rank,
-            local_row, deal_stride, *tail);
+            local_row, deal_stride, *flags);
     else
         combine_push_kernel<false><<<(int)blocks, kWave * kPushWaves, 0, (hipStream_t)stream>>>(
             (const uint8_t *)x, src_idx, total_rows_dev, rows_hint, H * 2, mi_ep_combine_row_bytes(H), K, W, pp, par, slot_rows, my_rank, local_row,
-            deal_stride, PushTail{});
+            deal_stride, PushFlags{});
     return launch_status();
 }
 
@@ -400,21 +358,6 @@ extern "C" int mi_ep_combine_push(const void *x, const int32_t *src_idx, const i
 {
     return combine_push_launch(x, src_idx, total_rows_dev, rows_hint, H, K, dst_base_host, W, slot_region_bytes, epoch_ctr, parity_stride, my_rank,
                                local_row, nullptr, stream);
-}
-
-extern "C" int mi_ep_combine_push_signal_wait(const void *x, const int32_t *src_idx, const int32_t *total_rows_dev, int rows_hint, int H, int K,
-                                              void *const *dst_base_host, int W, size_t slot_region_bytes, uint64_t *epoch_ctr,
-                                              size_t parity_stride, int my_rank, int32_t *local_row, uint64_t *const *peer_flags_host,
-                                              const uint64_t *my_flags, uint32_t *arrive_word, int32_t *status, int timeout_ms, void *stream)
-{
-    if (!epoch_ctr || !peer_flags_host || !my_flags || !arrive_word || !status || W <= 0 || W > MI_EP_MAX_RANKS || my_rank < 0 || my_rank >= W)
-        return MI_EP_EINVAL;
-    PushTail tail{};
-    tail.arrive = arrive_word, tail.my_flags = my_flags, tail.epoch_bump = epoch_ctr, tail.status = status;
-    tail.timeout_ticks = (uint64_t)(timeout_ms > 0 ? timeout_ms : 10000) * 100000ull;
-    if (!peer_ptrs(peer_flags_host, W, tail.flag_peers)) return MI_EP_EINVAL;
-    return combine_push_launch(x, src_idx, total_rows_dev, rows_hint, H, K, dst_base_host, W, slot_region_bytes, epoch_ctr, parity_stride, my_rank,
-                               local_row, &tail, stream);
 }
 
 // the push of the two-launch combine: mi_ep_combine_push whose waves raise the flag word of every row they have written at the row's owner
@@ -430,11 +373,11 @@ extern "C" int mi_ep_combine_push_flagged(const void *x, const int32_t *src_idx,
     // a slot without a flag word is no slot: (t, k) past the words of a half are dropped like those past the region
     const size_t flagged_bytes = (row_flags_parity_stride / sizeof(uint32_t)) * mi_ep_combine_row_bytes(H);
     slot_region_bytes = slot_region_bytes ? std::min(slot_region_bytes, flagged_bytes) : flagged_bytes;
-    PushTail tail{};
-    tail.epoch_bump = const_cast<uint64_t *>(epoch_ctr), tail.row_flags_parity_stride = row_flags_parity_stride, tail.cur_epoch = cur_epoch_word;
-    if (!peer_ptrs(peer_row_flags_host, W, tail.row_flag_peers)) return MI_EP_EINVAL;
+    PushFlags flags{};
+    flags.epoch_bump = epoch_ctr, flags.row_flags_parity_stride = row_flags_parity_stride, flags.cur_epoch = cur_epoch_word;
+    if (!peer_ptrs(peer_row_flags_host, W, flags.row_flag_peers)) return MI_EP_EINVAL;
     return combine_push_launch(x, src_idx, total_rows_dev, rows_hint, H, K, dst_base_host, W, slot_region_bytes, epoch_ctr, parity_stride, my_rank,
-                               local_row, &tail, stream);
+                               local_row, &flags, stream);
 }
 
 static int combine_reduce_launch(const void *slots, const void *topk_idx, int idx_is_i32, const float *topk_weights,

@@ -381,8 +381,8 @@ __device__ __forceinline__ void stage_body(
         uint8_t *row = (uint8_t *)dsts.p[drank] + poff + (size_t)slot * stride;
         u32x4 meta = u32x4{__float_as_uint(scale_out), (uint32_t)t, (uint32_t)k, (uint32_t)my_rank};
         if constexpr (LATE) {
-            // one-launch low-latency form: the rows are announced to their owners from INSIDE this launch (ll_layout_send_kernel's tail), so
-            // they are written through the caches (sc0 sc1) -- the announcing workgroup then needs no release fence, only every wave's drain
+            // one-launch low-latency form (ll_layout_send_kernel): a tagged row is announced to its owner from INSIDE this launch, by its own
+            // meta word, so the rows are written through the caches (sc0 sc1) -- the announcing wave then needs no release fence, only its drain
             const StWT st{row_rsrc(row, pl.meta_off() + MI_EP_ROW_META_BYTES), 0u};
             st_quant_row<QM>(st, nullptr, false, H, q, sc, lane);
             if (late.tag) {                                 // tagged rows: the payload is at its owner before the meta word says so
@@ -449,17 +449,20 @@ __device__ __forceinline__ void write_count_tables(const int32_t *c, int L, int 
     }
 }
 
-// The count exchange of a low-latency dispatch, run by ONE workgroup (of any size up to 1024 threads): post this rank's per-expert counts
-// to every peer (optional), wait (bounded) for the L*W count granules of this call's epoch, inclusive cumsum in idx-i order, per-expert
-// counts, and complete the family's call counter.  c = LDS, L*W + 16 words.
-__device__ __forceinline__ void ll_counts_body(int32_t *c, const PeerPtrs &count_peers, const int32_t *__restrict__ my_counts_out /*[E] or null*/,
-                                               int my_rank, const uint64_t *__restrict__ granules_base, uint64_t ep64,
-                                               size_t counts_parity_stride, uint64_t *epoch_bump, int L, int W, int count_type,
-                                               int32_t *__restrict__ layout_range, int64_t *__restrict__ packed_recv_count, int32_t *status,
-                                               uint64_t timeout_ticks)
+// The count exchange of a low-latency dispatch, run by ONE workgroup: post this rank's per-expert counts to every peer (optional), wait
+// (bounded) for the L*W count granules of this call's epoch, inclusive cumsum in idx-i order, per-expert counts, and complete the
+// family's call counter.
+__global__ __launch_bounds__(256) void ll_counts_kernel(PeerPtrs count_peers, const int32_t *__restrict__ my_counts_out /*[E] or null*/,
+                                                        int my_rank, const uint64_t *__restrict__ granules_base, EpochRef er,
+                                                        size_t counts_parity_stride, uint64_t *epoch_bump, int L, int W,
+                                                        int count_type, int32_t *__restrict__ layout_range,
+                                                        int64_t *__restrict__ packed_recv_count, int32_t *status,
+                                                        uint64_t timeout_ticks)
 {
+    extern __shared__ __attribute__((aligned(16))) int32_t c[];   // [L*W] counts -> inclusive cumsum, then [16] wave totals
     const int LW = L * W, tid = threadIdx.x;
     // this call's epoch (device-resident counter + 1, or the explicit value) and the ping-pong half of the count granules
+    const uint64_t ep64 = epoch_of(er);
     const uint32_t epoch = (uint32_t)ep64;
     const size_t cpoff = (size_t)(ep64 & 1ull) * counts_parity_stride;
     const uint64_t *granules = (const uint64_t *)((const uint8_t *)granules_base + cpoff);
@@ -490,24 +493,15 @@ __device__ __forceinline__ void ll_counts_body(int32_t *c, const PeerPtrs &count
     if (epoch_bump && tid == 0) *epoch_bump = ep64;
 }
 
-// The count exchange raised from INSIDE the layout + send launch (ll_layout_send_kernel with a tail): every workgroup -- the send
-// workgroups after their write-through rows have drained, the layout workgroup after an agent-scope release of its tables -- counts
-// itself in at a device word of the rank's control area; the last one to arrive runs ll_counts_body and re-arms the word.  One launch
-// and one kernel boundary less per low-latency dispatch (three launches -> two).
-struct LLTail {
-    uint32_t *arrive;             // NULL: no tail (the count exchange is a launch of its own)
+// What the TAGGED form of the layout + send launch posts (mi_ep_ll_dispatch_layout_send_tagged; cur_epoch == NULL: the plain form, nothing
+// is posted and the rows carry no tag).  Nobody waits for anybody in this launch -- the layout workgroup posts this rank's per-expert
+// counts to the peers as soon as it has them and leaves the call's epoch at *cur_epoch, the send waves tag their rows; the packing launch
+// (ll_wait_pack_kernel) collects counts and rows itself.
+struct LLTagPost {
     PeerPtrs count_peers;
-    const uint64_t *granules_base;
     size_t counts_parity_stride;
-    uint64_t *epoch_bump;         // the family's completed-call counter (this call's epoch = counter + 1)
-    int L, count_type;
-    int32_t *layout_range;
-    int64_t *packed_recv_count;
-    int32_t *status;
-    uint64_t timeout_ticks;
-    // TAGGED form (arrive == NULL, cur_epoch set; mi_ep_ll_dispatch_layout_send_tagged): nobody waits for anybody in this launch -- the layout
-    // workgroup posts this rank's per-expert counts to the peers as soon as it has them and leaves the call's epoch at *cur_epoch, the send
-    // waves tag their rows; the packing launch (ll_wait_pack_kernel) collects counts and rows itself.
+    const uint64_t *epoch_bump;   // the family's completed-call counter (this call's epoch = counter + 1)
+    int L;
     uint64_t *cur_epoch;
 };
 
@@ -521,25 +515,24 @@ __global__ __launch_bounds__(1024) void ll_layout_send_kernel(
     const uint16_t *__restrict__ x, const void *__restrict__ topk_idx, int T, int K, int H, int E, int W, int nbits, int my_rank, PeerPtrs dsts,
     LLGeom ll, Parity par, int32_t *__restrict__ num_tokens_per_rank, int32_t *__restrict__ num_tokens_per_expert,
     int32_t *__restrict__ is_token_in_rank, int32_t *__restrict__ send_token_idx_small, int32_t *__restrict__ send_data_offset, int send_waves,
-    LLTail tail)
+    LLTagPost post)
 {
     extern __shared__ __attribute__((aligned(16))) int32_t smem[];
     if (blockIdx.x == 0) {
         layout_small_body<I32, UT>(topk_idx, T, K, E, W, nbits, num_tokens_per_rank, num_tokens_per_expert, is_token_in_rank,
                                    send_token_idx_small, send_data_offset, nullptr, nullptr, smem, 1, 0);
-        if (tail.cur_epoch) {
+        if (post.cur_epoch) {
             __syncthreads();                                    // num_tokens_per_expert as this workgroup wrote it
-            const uint64_t ep64 = *tail.epoch_bump + 1ull;
-            const size_t cpoff = (size_t)(ep64 & 1ull) * tail.counts_parity_stride;
-            const int L = tail.L;
+            const uint64_t ep64 = *post.epoch_bump + 1ull;
+            const size_t cpoff = (size_t)(ep64 & 1ull) * post.counts_parity_stride;
+            const int L = post.L;
             for (int i = threadIdx.x; i < L * W; i += blockDim.x) {
                 const int d = i / L, le = i % L;
-                sys_store_u64_relaxed((uint64_t *)((uint8_t *)tail.count_peers.p[d] + cpoff) + (size_t)le * W + my_rank,
+                sys_store_u64_relaxed((uint64_t *)((uint8_t *)post.count_peers.p[d] + cpoff) + (size_t)le * W + my_rank,
                                       ((uint64_t)(uint32_t)ep64 << 32) | (uint32_t)num_tokens_per_expert[d * L + le]);
             }
-            if (threadIdx.x == 0) *tail.cur_epoch = ep64;
+            if (threadIdx.x == 0) *post.cur_epoch = ep64;
         }
-        if (!tail.arrive) return;
     } else {
         const int npairs = T * K;
         for (int i = threadIdx.x; i < npairs; i += blockDim.x) {
@@ -552,34 +545,10 @@ __global__ __launch_bounds__(1024) void ll_layout_send_kernel(
         const int wave = (int)(threadIdx.x / kWave);
         const int wid = (int)(blockIdx.x - 1) * send_waves + wave;
         if (wave < send_waves && wid < npairs) {
-            const LateIdx late{smem, wid % K, tail.cur_epoch ? ll_row_tag(*tail.epoch_bump + 1ull) : 0u};
+            const LateIdx late{smem, wid % K, post.cur_epoch ? ll_row_tag(*post.epoch_bump + 1ull) : 0u};
             stage_body<I32, QM, true>(x, topk_idx, nullptr, nullptr, T, K, H, E, my_rank, dsts, ll, K, (size_t)0, PushGeom{0, 0}, par, wid, late);
         }
-        if (!tail.arrive) return;
     }
-    // ---- tail: count this workgroup in; the last one runs the count exchange
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // every wave: its (write-through) stores are performed
-    __syncthreads();
-    uint32_t *const last_s = (uint32_t *)smem;                  // (the routing table / layout tables are done with)
-    if (threadIdx.x == 0) {
-        // the layout workgroup's tables were plain stores: release them to the device (num_tokens_per_expert is read by the tail, possibly
-        // on another XCD; the other tables by later launches)
-        if (blockIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        const uint32_t old = __hip_atomic_fetch_add(tail.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *last_s = old == gridDim.x - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (*(volatile uint32_t *)last_s == 0) return;
-    __syncthreads();                                            // (everybody has read the word before the body reuses the LDS)
-    if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // num_tokens_per_expert as the layout workgroup wrote it
-    __syncthreads();
-    const uint64_t ep64 = *tail.epoch_bump + 1ull;
-    ll_counts_body(smem, tail.count_peers, num_tokens_per_expert, my_rank, tail.granules_base, ep64, tail.counts_parity_stride, tail.epoch_bump,
-                   tail.L, W, tail.count_type, tail.layout_range, tail.packed_recv_count, tail.status, tail.timeout_ticks);
-    if (threadIdx.x == 0) __hip_atomic_store(tail.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1375,19 +1344,6 @@ __global__ void ll_post_counts_kernel(PeerPtrs peers, const int32_t *__restrict_
         sys_store_u64_relaxed(g + (size_t)le * W + my_rank, ((uint64_t)epoch << 32) | (uint32_t)cnt[d * L + le]);
 }
 
-// one workgroup: wait for the L*W count granules, inclusive cumsum in idx-i order, per-expert counts (ll_counts_body, above)
-__global__ __launch_bounds__(256) void ll_counts_kernel(PeerPtrs count_peers, const int32_t *__restrict__ my_counts_out /*[E] or null*/,
-                                                        int my_rank, const uint64_t *__restrict__ granules_base, EpochRef er,
-                                                        size_t counts_parity_stride, uint64_t *epoch_bump, int L, int W,
-                                                        int count_type, int32_t *__restrict__ layout_range,
-                                                        int64_t *__restrict__ packed_recv_count, int32_t *status,
-                                                        uint64_t timeout_ticks)
-{
-    extern __shared__ __attribute__((aligned(16))) int32_t c[];   // [L*W] counts -> inclusive cumsum, then [16] wave totals
-    ll_counts_body(c, count_peers, my_counts_out, my_rank, granules_base, epoch_of(er), counts_parity_stride, epoch_bump, L, W, count_type,
-                   layout_range, packed_recv_count, status, timeout_ticks);
-}
-
 }  // namespace mi_ep
 
 extern "C" int mi_ep_ll_dispatch_send(const void *x, const void *topk_idx, int idx_is_i32,
@@ -1409,7 +1365,7 @@ extern "C" int mi_ep_ll_dispatch_send(const void *x, const void *topk_idx, int i
 static int ll_layout_send_launch(const void *x, const void *topk_idx, int idx_is_i32, int T, int K, int H, int E, int W, int my_rank,
                                  int max_tokens, int quant_mode, void *const *peer_rows_host, const uint64_t *epoch_ctr,
                                  size_t parity_stride, int32_t *num_tokens_per_rank, int32_t *num_tokens_per_expert,
-                                 int32_t *is_token_in_rank, int32_t *send_token_idx_small, int32_t *send_data_offset, const LLTail *tail_in,
+                                 int32_t *is_token_in_rank, int32_t *send_token_idx_small, int32_t *send_data_offset, const LLTagPost *post_in,
                                  void *stream)
 {
     if (T < 0 || K <= 0 || K > MI_EP_MAX_TOPK || H <= 0 || H % 16 || H > MI_EP_MAX_HIDDEN || E <= 0 || W <= 0 ||
@@ -1430,10 +1386,9 @@ static int ll_layout_send_launch(const void *x, const void *topk_idx, int idx_is
     static const int send_waves_env = getenv("MI_EP_LL_SEND_WAVES") ? atoi(getenv("MI_EP_LL_SEND_WAVES")) : 0;
     const int send_waves = send_waves_env >= 1 && send_waves_env <= 16 ? send_waves_env : kLLSendWaves;
     const int blocks = 1 + (int)(((long long)T * K + send_waves - 1) / send_waves);       // the layout workgroup + the send workgroups
+    const LLTagPost post = post_in ? *post_in : LLTagPost{};
     // dynamic LDS: the layout workgroup's tables, or the send workgroups' copy of the routing table (int32 per pair)
-    const LLTail tail = tail_in ? *tail_in : LLTail{};
-    // dynamic LDS: the layout workgroup's tables, the send workgroups' copy of the routing table (int32 per pair), the tail's counts
-    const size_t lds = std::max(std::max(layout_small_lds_bytes(E, W, ut), (size_t)T * K * sizeof(int32_t)), tail_in ? (size_t)(E + 16) * 4 : (size_t)0);
+    const size_t lds = std::max(layout_small_lds_bytes(E, W, ut), (size_t)T * K * sizeof(int32_t));
     const uint16_t *xp = (const uint16_t *)x;
     // the kernel of quant mode qm (low-latency: modes 0-3), index width and layout unit (16 or kLayoutUnitTokens tokens)
     auto with_kernel = [](int qm, bool i32, bool ut16, auto f) {
@@ -1450,7 +1405,7 @@ static int ll_layout_send_launch(const void *x, const void *topk_idx, int idx_is
                 });
     if (!with_kernel(quant_mode, idx_is_i32, ut == 16, [&](auto k) {
             k<<<blocks, 1024, lds, s>>>(xp, topk_idx, T, K, H, E, W, nbits, my_rank, pp, ll, par, num_tokens_per_rank, num_tokens_per_expert,
-                                        is_token_in_rank, send_token_idx_small, send_data_offset, send_waves, tail);
+                                        is_token_in_rank, send_token_idx_small, send_data_offset, send_waves, post);
         }))
         return MI_EP_EINVAL;
     return launch_status();
@@ -1467,29 +1422,6 @@ extern "C" int mi_ep_ll_dispatch_layout_send(const void *x, const void *topk_idx
                                  stream);
 }
 
-// layout + send + the count exchange in ONE launch (the tail of ll_layout_send_kernel); mi_ep_ll_pack then fills the outputs
-extern "C" int mi_ep_ll_dispatch_layout_send_counts(const void *x, const void *topk_idx, int idx_is_i32, int T, int K, int H, int E, int W,
-                                                   int my_rank, int max_tokens, int quant_mode, void *const *peer_rows_host,
-                                                   uint64_t *epoch_ctr, size_t parity_stride, int32_t *num_tokens_per_rank,
-                                                   int32_t *num_tokens_per_expert, int32_t *is_token_in_rank, int32_t *send_token_idx_small,
-                                                   int32_t *send_data_offset, uint64_t *const *peer_counts_host, const uint64_t *my_counts,
-                                                   size_t counts_parity_stride, int count_type, int32_t *layout_range,
-                                                   int64_t *packed_recv_count, uint32_t *arrive_word, int32_t *status, int timeout_ms,
-                                                   void *stream)
-{
-    if (!epoch_ctr || !peer_counts_host || !my_counts || !layout_range || !packed_recv_count || !arrive_word || !status || W <= 0 ||
-        W > MI_EP_MAX_RANKS || E <= 0 || E % W || E > 2048)
-        return MI_EP_EINVAL;
-    LLTail tail{};
-    tail.arrive = arrive_word, tail.granules_base = my_counts, tail.counts_parity_stride = counts_parity_stride, tail.epoch_bump = epoch_ctr;
-    tail.L = E / W, tail.count_type = count_type, tail.layout_range = layout_range, tail.packed_recv_count = packed_recv_count;
-    tail.status = status, tail.timeout_ticks = (uint64_t)(timeout_ms > 0 ? timeout_ms : 10000) * 100000ull;
-    if (!peer_ptrs(peer_counts_host, W, tail.count_peers)) return MI_EP_EINVAL;
-    return ll_layout_send_launch(x, topk_idx, idx_is_i32, T, K, H, E, W, my_rank, max_tokens, quant_mode, peer_rows_host, epoch_ctr, parity_stride,
-                                 num_tokens_per_rank, num_tokens_per_expert, is_token_in_rank, send_token_idx_small, send_data_offset, &tail,
-                                 stream);
-}
-
 // layout + send with TAGGED rows and the counts posted from the head of the launch (no count exchange launch: mi_ep_ll_wait_pack follows)
 extern "C" int mi_ep_ll_dispatch_layout_send_tagged(const void *x, const void *topk_idx, int idx_is_i32, int T, int K, int H, int E, int W,
                                                    int my_rank, int max_tokens, int quant_mode, void *const *peer_rows_host,
@@ -1499,11 +1431,11 @@ extern "C" int mi_ep_ll_dispatch_layout_send_tagged(const void *x, const void *t
                                                    uint64_t *cur_epoch_word, void *stream)
 {
     if (!epoch_ctr || !peer_counts_host || !cur_epoch_word || W <= 0 || W > MI_EP_MAX_RANKS || E <= 0 || E % W || E > 2048) return MI_EP_EINVAL;
-    LLTail tail{};
-    tail.counts_parity_stride = counts_parity_stride, tail.epoch_bump = const_cast<uint64_t *>(epoch_ctr), tail.L = E / W, tail.cur_epoch = cur_epoch_word;
-    if (!peer_ptrs(peer_counts_host, W, tail.count_peers)) return MI_EP_EINVAL;
+    LLTagPost post{};
+    post.counts_parity_stride = counts_parity_stride, post.epoch_bump = epoch_ctr, post.L = E / W, post.cur_epoch = cur_epoch_word;
+    if (!peer_ptrs(peer_counts_host, W, post.count_peers)) return MI_EP_EINVAL;
     return ll_layout_send_launch(x, topk_idx, idx_is_i32, T, K, H, E, W, my_rank, max_tokens, quant_mode, peer_rows_host, epoch_ctr, parity_stride,
-                                 num_tokens_per_rank, num_tokens_per_expert, is_token_in_rank, send_token_idx_small, send_data_offset, &tail,
+                                 num_tokens_per_rank, num_tokens_per_expert, is_token_in_rank, send_token_idx_small, send_data_offset, &post,
                                  stream);
 }
 
@@ -1532,27 +1464,6 @@ extern "C" int mi_ep_ll_wait_pack(const void *my_rows, const uint64_t *my_counts
         (const uint8_t *)my_rows, my_counts, counts_parity_stride, rows_parity_stride, cur_epoch_word, epoch_ctr, max_tokens, W, L, pl.data, count_type,
         (uint8_t *)packed_recv_x, packed_recv_x_scales, src_info, layout_range, packed_recv_count, cap, status,
         (uint64_t)(timeout_ms > 0 ? timeout_ms : 10000) * 100000ull);
-    return launch_status();
-}
-
-// the packing half of mi_ep_ll_post_recv on its own: rows from this rank's slabs into the packed outputs, by the cumulative counts the
-// count exchange left in layout_range (device); epoch_ctr = the family's call counter, already completed for this call (add = 0)
-extern "C" int mi_ep_ll_pack(const void *my_rows, const int32_t *layout_range, int W, int L, int max_tokens, int H, int quant_mode,
-                             void *packed_recv_x, float *packed_recv_x_scales, int32_t *src_info, int rows_capacity, const uint64_t *epoch_ctr,
-                             size_t rows_parity_stride, void *stream)
-{
-    if (quant_is_mx(quant_mode)) return MI_EP_EINVAL;            // low-latency dispatch: quant modes 0-3 (include/mi_ep.h)
-    if (!my_rows || !layout_range || !packed_recv_x || !src_info || W <= 0 || W > MI_EP_MAX_RANKS || L <= 0 || L * W > 2048 || H <= 0 || H % 16 ||
-        max_tokens <= 0)
-        return MI_EP_EINVAL;
-    PeerPtrs pp;
-    for (int i = 0; i < W; ++i) pp.p[i] = const_cast<void *>(my_rows);
-    const int cap = rows_capacity > 0 ? rows_capacity : L * W * max_tokens;      // rows the caller's output buffers hold
-    const RowPayload pl = row_payload(H, quant_mode);
-    const long long blocks = std::max(pull_blocks((long long)L * W * max_tokens, 256 * 8), 1ll);
-    pull_kernel<<<(int)blocks, kWave * kPullWaves, (size_t)L * W * 4, (hipStream_t)stream>>>(pp, layout_range, nullptr, max_tokens, W, L * W, pl,
-                                                                                         (uint8_t *)packed_recv_x, packed_recv_x_scales, src_info,
-                                                                                         cap, make_parity(epoch_ctr, 0, rows_parity_stride));
     return launch_status();
 }
 

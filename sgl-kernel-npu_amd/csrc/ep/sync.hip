@@ -34,17 +34,15 @@ __global__ void wait_kernel(const uint64_t *__restrict__ flags, int W, uint64_t 
 }
 
 __global__ void notify_post_kernel(PeerPtrs peers, int W, int my_rank, int E, const int32_t *__restrict__ cnt,
-                                   int num_tokens, uint32_t epoch, PeerPtrs sig_peers, uint64_t sig_epoch)
+                                   int num_tokens, uint32_t epoch)
 {
-    // grid.x = W destinations, threads sweep the E+1 values; sig_epoch != 0 also raises this rank's "rows staged" flag
-    // at the destination (the fused form of notify_post + signal: both only need the preceding kernel boundary)
+    // grid.x = W destinations, threads sweep the E+1 values
     const int d = blockIdx.x;
     uint64_t *row = (uint64_t *)peers.p[d] + (size_t)my_rank * (E + 1);
     for (int e = threadIdx.x; e <= E; e += blockDim.x) {
         const uint32_t v = (e < E) ? (uint32_t)cnt[e] : (uint32_t)num_tokens;
         sys_store_u64_relaxed(row + e, ((uint64_t)epoch << 32) | v);
     }
-    if (sig_epoch && threadIdx.x == 0) sys_store_u64((uint64_t *)sig_peers.p[d] + my_rank, sig_epoch);
 }
 
 // signal + wait in one launch (combine: rows pushed -> tell every owner, then wait for every expert rank)
@@ -252,20 +250,7 @@ extern "C" int mi_ep_notify_post(uint64_t *const *peer_notify_host, int W, int m
     if (fill_peers(pp, (const void *const *)peer_notify_host, W) || my_rank < 0 || my_rank >= W || E <= 0 ||
         !num_tokens_per_expert || epoch == 0)
         return MI_EP_EINVAL;
-    notify_post_kernel<<<W, 256, 0, (hipStream_t)stream>>>(pp, W, my_rank, E, num_tokens_per_expert, num_tokens, epoch, pp, 0);
-    return launch_status();
-}
-
-extern "C" int mi_ep_notify_post_signal(uint64_t *const *peer_notify_host, uint64_t *const *peer_flags_host, int W, int my_rank,
-                                        int E, const int32_t *num_tokens_per_expert, int num_tokens, uint32_t notify_epoch,
-                                        uint64_t signal_epoch, void *stream)
-{
-    PeerPtrs pp, sp;
-    if (fill_peers(pp, (const void *const *)peer_notify_host, W) || fill_peers(sp, (const void *const *)peer_flags_host, W) ||
-        my_rank < 0 || my_rank >= W || E <= 0 || !num_tokens_per_expert || notify_epoch == 0 || signal_epoch == 0)
-        return MI_EP_EINVAL;
-    notify_post_kernel<<<W, 256, 0, (hipStream_t)stream>>>(pp, W, my_rank, E, num_tokens_per_expert, num_tokens, notify_epoch, sp,
-                                                           signal_epoch);
+    notify_post_kernel<<<W, 256, 0, (hipStream_t)stream>>>(pp, W, my_rank, E, num_tokens_per_expert, num_tokens, epoch);
     return launch_status();
 }
 
@@ -305,27 +290,6 @@ extern "C" int mi_ep_notify_tables(const int32_t *cnt_matrix, int W, int E, int 
                                                               recv_offset, recv_tokens_per_expert, expert_global_offset,
                                                               srcrank_in_expert_offset, r_in_srcrank_offset,
                                                               total_recv_token, max_bs, pull_offset, summary_host);
-    return launch_status();
-}
-
-extern "C" int mi_ep_notify_wait_tables(const uint64_t *my_notify, uint32_t notify_epoch, const uint64_t *my_flags,
-                                        uint64_t flag_epoch, int32_t *cnt_matrix, int W, int E, int my_rank, int relative_pull,
-                                        int32_t *recv_count, int32_t *recv_offset, int32_t *recv_tokens_per_expert,
-                                        int32_t *expert_global_offset, int32_t *srcrank_in_expert_offset,
-                                        int32_t *r_in_srcrank_offset, int32_t *total_recv_token, int32_t *max_bs,
-                                        int32_t *pull_offset, int32_t *summary_host, int32_t *status, int timeout_ms,
-                                        int32_t *wait_cost_stats, void *stream)
-{
-    if (!my_notify || !cnt_matrix || !status || notify_epoch == 0 || W <= 0 || W > MI_EP_MAX_RANKS || E <= 0 || E % W || E > 2048 ||
-        my_rank < 0 || my_rank >= W)
-        return MI_EP_EINVAL;
-    const size_t lds = notify_lds_bytes(W, E);
-    if (lds > kNotifyLdsMax) return MI_EP_EINVAL;
-    NotifyPost none{};
-    notify_wait_tables_kernel<<<1, 1024, lds, (hipStream_t)stream>>>(
-        none, my_notify, notify_epoch, my_flags, flag_epoch, nullptr, nullptr, 0, cnt_matrix, W, E, my_rank, relative_pull, recv_count, recv_offset,
-        recv_tokens_per_expert, expert_global_offset, srcrank_in_expert_offset, r_in_srcrank_offset, total_recv_token, max_bs,
-        pull_offset, summary_host, status, ms_to_ticks(timeout_ms), wait_cost_stats);
     return launch_status();
 }
 

@@ -262,6 +262,8 @@ def _gpu_ll_empty_rank(rank, world, port, cfg):
         buf = deep_ep.Buffer(group, low_latency_mode=True)
     if extra.get("own_gpu"):
         buf.runtime.set_ranks_share_device(False)
+    if forms == ("1", "1"):          # the retired value: three launches
+        assert list(buf.runtime.get_low_latency_default_forms()) == [0, 0]
     if "stale_rank" in extra and W > 1:
         # the windows passed their first leg, the in-launch hand-off did not: the low-latency calls keep the window strategies on their
         # three-launch forms, whatever the env asks for, and the Buffer said so

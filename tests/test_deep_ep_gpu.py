@@ -96,13 +96,13 @@ def test_low_latency_calls_replay_in_a_captured_graph(cfg):
     _spawn(mp_workers.gpu_graph_worker, cfg[0], cfg)
 
 
-@pytest.mark.parametrize("forms", [("1", "1"), ("0", "0"), ("1", "0"), ("0", "2"), ("2", "2"), ("2", "0")],
-                         ids=["tails", "launches", "dispatch_tail_only", "combine_row_flags", "tagged_rows_and_row_flags", "dispatch_tagged_rows_only"])
+@pytest.mark.parametrize("forms", [("0", "0"), ("0", "2"), ("2", "2"), ("2", "0")],
+                         ids=["launches", "combine_row_flags", "tagged_rows_and_row_flags", "dispatch_tagged_rows_only"])
 @pytest.mark.parametrize("cfg", [(2, 24, 512, 128, 4, 8, 2), (4, 17, 1024, 128, 8, 32, 2)])
 def test_low_latency_launch_forms(cfg, forms):
-    """The count exchange of a low-latency dispatch and the "rows pushed" signal + wait of a combine, each either as the TAIL of the
-    launch in front of it (the last workgroup to arrive does it: MI_EP_LL_FUSED_COUNTS / MI_EP_COMBINE_FUSED = 1) or as a launch of its
-    own (= 0): same rows, tables and sums, bit-exact against the oracle, eagerly and replayed from a captured graph.  MI_EP_COMBINE_FUSED = 2:
+    """The launch forms of a low-latency dispatch and combine (MI_EP_LL_FUSED_COUNTS / MI_EP_COMBINE_FUSED), each pair of them: same rows, tables
+    and sums, bit-exact against the oracle, eagerly and replayed from a captured graph.  0: the count exchange of the dispatch and the "rows
+    pushed" signal + wait of the combine as launches of their own.  MI_EP_COMBINE_FUSED = 2:
     the two-launch combine whose pushed rows raise their own flag words and whose reduce waits per selection (no exchange in between);
     MI_EP_LL_FUSED_COUNTS = 2: the two-launch dispatch whose rows carry the call's tag and whose packing launch collects counts and rows itself."""
     import os
@@ -120,7 +120,7 @@ def test_low_latency_launch_forms(cfg, forms):
 
 
 @pytest.mark.parametrize("forms", [("0", "0"), ("2", "2"), ("1", "1"), ("2", "0"), ("0", "2")],
-                         ids=["three_launches", "two_launches", "tails", "tagged_dispatch_three_launch_combine", "three_launch_dispatch_flagged_combine"])
+                         ids=["three_launches", "two_launches", "retired_value_1_takes_three_launches", "tagged_dispatch_three_launch_combine", "three_launch_dispatch_flagged_combine"])
 @pytest.mark.parametrize("cfg", [(1, 0, 512, 4, 8, True), (2, 0, 1024, 4, 8, True), (4, 0, 512, 8, 32, False)])      # W, T of rank 0, H, K, E, quant
 def test_low_latency_pair_with_a_rank_without_tokens(cfg, forms):
     """Rank r brings T + r tokens, rank 0 none at all: its send launch still posts its (zero) counts and leaves the call's epoch, its combine
