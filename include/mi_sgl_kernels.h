@@ -7,7 +7,8 @@
  *   mi_mla_decode            <- attention/decode_attention.py:5-230   (_paged_mla_fwd_kernel / decode_mla)
  *   mi_gqa_decode            <- attention/decode_attention.py:233-450,646-760 (decode_gqa, decode_gqa_high_performance)
  *   mi_gqa_decode_sinks      <- attention/sinks_attention.py:7-286 (attention_sinks_triton, attention_sinks_prefill_triton)
- *   mi_swiglu_quant          <- activation/swiglu_quant.py:8-127      (_swiglu_quant_kernel / swiglu_quant)
+ *   mi_gqa_sparse_decode     <- attention/gqa_share_sparse_attention.py:180-878 (flash_decode_bnsd_with_gqa_share_sparse)
+ *   mi_swiglu_quant          <- activation/swiglu_quant.py:8-127     (_swiglu_quant_kernel / swiglu_quant)
  *   mi_add_rmsnorm_bias      <- norm/add_rmsnorm_bias.py:8-147        (add_rmsnorm_bias_kernel / add_rmsnorm_bias)
  *                               norm/add_rmsnorm_bias.py:150-232      (add_gemma_rms_norm)
  *   mi_split_qkv_rmsnorm_rope<- norm/split_qkv_rmsnorm_rope.py:8-438  (split_qkv_rmsnorm_rope)
@@ -134,6 +135,35 @@ int mi_gqa_decode_sinks(const void *q, const void *k, const void *v, void *out, 
                         int64_t v_stride_row, int64_t v_stride_h, int64_t o_stride_b, int64_t o_stride_h, float sm_scale, int dtype, int num_splits,
                         void *workspace, size_t workspace_bytes, const void *sinks, int sinks_dtype, int sliding_window,
                         const int32_t *block_table_rows, void *stream);
+
+/* ---- block-sparse GQA decode over top-k selected KV blocks (attention/gqa_share_sparse_attention.py:180-546, 635-878) ------------
+ * Per (b, h), kh = h / (q_heads / kv_heads), seq_len = min(seq_lens[b], max_kv_len): every slot t with lb = topk_idx[kh, b, t] >= 0 and
+ * lb * block_size < seq_len names a page -- block_table[b, lb], or req_to_token[req_pool_indices[b], min(lb * block_size, rtt_cols - 1)] /
+ * block_size (clamped to [0, num_pages - 1] when sanitize_page_ids) -- whose keys n with lb * block_size + n < seq_len take part with logit
+ * (q[b,h] . k[page, n, kh]) * sm_scale.  Any other slot contributes nothing and its table entry is not read; duplicates count twice.
+ * sink [q_heads, head_dim] (rows sink_stride_h apart, sink_dtype MI_DTYPE_*; NULL = none): one more logit (q[b,h] . sink[h]) * sm_scale,
+ * in fp32, in the maximum and the denominator, without a value row.  out = softmax-weighted v (P rounded to the cache dtype before P.V);
+ * a row without a key is zeros.
+ *   q, out [batch, q_heads, head_dim]; k, v [pages, block_size, kv_heads, head_dim]; strides in elements, last dims contiguous;
+ *   topk_idx through its three strides (per-q-head lists: pass the q-head stride times the group size); exactly one of block_table and
+ *   (req_to_token, req_pool_indices) is non-NULL; the *_is_i64 flags tell int64 from int32 elements.
+ *   head_dim a multiple of 8 up to 256; block_size 16, 32, 64 or 128; sm_scale > 0; max_kv_len = table columns * block_size.
+ * num_chunks: pieces of the top-k list per (b, kv head), 1 <= num_chunks <= max(1, topk); 0 = mi_gqa_sparse_decode_num_chunks (shapes and
+ * CU count only).  More than one chunk needs mi_gqa_sparse_decode_workspace() bytes, 16-byte aligned, for the fp32 partials and runs a merge
+ * launch behind the attention launch.  Nothing is read back: capturable in a graph.  MI_SGL_ENOTAPPLICABLE when a chunk holds more than
+ * 1024 list slots (ask for more chunks). */
+size_t mi_gqa_sparse_decode_workspace(int batch, int q_heads, int head_dim, int num_chunks);
+int mi_gqa_sparse_decode_num_chunks(int batch, int kv_heads, int topk);
+int mi_gqa_sparse_decode(const void *q, const void *k, const void *v, void *out, const int32_t *seq_lens, const void *topk_idx,
+                         int topk_is_i64, int64_t topk_stride_h, int64_t topk_stride_b, int64_t topk_stride_t,
+                         const void *block_table, int block_table_is_i64, int64_t bt_stride_b, int64_t bt_stride_n,
+                         const void *req_to_token, int req_to_token_is_i64, int64_t rtt_stride_r, int64_t rtt_stride_t, int rtt_cols,
+                         const void *req_pool_indices, int req_pool_is_i64, const void *sink, int sink_dtype, int64_t sink_stride_h,
+                         int batch, int q_heads, int kv_heads, int head_dim, int block_size, int topk, int max_kv_len, int num_pages,
+                         int sanitize_page_ids, int64_t q_stride_b, int64_t q_stride_h, int64_t k_stride_blk, int64_t k_stride_row,
+                         int64_t k_stride_h, int64_t v_stride_blk, int64_t v_stride_row, int64_t v_stride_h, int64_t o_stride_b,
+                         int64_t o_stride_h, float sm_scale, int dtype, int num_chunks, void *workspace, size_t workspace_bytes,
+                         void *stream);
 
 /* ---- SwiGLU + per-row INT8 quantisation (swiglu_quant.py:87-127) -------------------------------------------------
  * x [rows, cols] (cols = 2I; gate = x[:, :I], up = x[:, I:]); only the first `total` rows are processed, where total =

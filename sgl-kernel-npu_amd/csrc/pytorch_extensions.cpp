@@ -320,6 +320,81 @@ at::Tensor fia_blockq_sparse_prefill(const at::Tensor &q, const at::Tensor &k_ca
     return out;
 }
 
+// attention/gqa_share_sparse_attention.py:635-878: block-sparse GQA decode over the top-k selected KV blocks (csrc/kernels/gqa_sparse_decode.hip).
+// topk_idx [Hkv or Hq, B, topk] (per-q-head lists: the list of each group's first head is used, :734-739); exactly one of block_table and
+// (req_to_token, req_pool_indices, max_num_blocks, num_pages); num_chunks 0 = the library's choice.  Returns [B, Hq, D].
+at::Tensor gqa_share_sparse_decode(const at::Tensor &q, const std::optional<at::Tensor> &sink, const at::Tensor &k_cache, const at::Tensor &v_cache,
+                                   const std::optional<at::Tensor> &block_table, const at::Tensor &seq_lens, const at::Tensor &topk_idx,
+                                   double sm_scale, int64_t num_chunks, const std::optional<at::Tensor> &req_to_token,
+                                   const std::optional<at::Tensor> &req_pool_indices, int64_t max_num_blocks, int64_t num_pages,
+                                   bool sanitize_page_ids)
+{
+    const c10::DeviceGuard device_guard(q.device());
+    auto is_index = [](const at::Tensor &t) { return t.scalar_type() == at::kInt || t.scalar_type() == at::kLong; };
+    TORCH_CHECK(q.dim() == 3 && k_cache.dim() == 4 && v_cache.dim() == 4 && topk_idx.dim() == 3 && seq_lens.dim() == 1,
+                "gqa_share_sparse_decode: q [B, Hq, D], caches [pages, block, Hkv, D], topk_idx [H, B, topk], seq_lens [B]");
+    TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "gqa_share_sparse_decode: q must be fp16 or bf16");
+    TORCH_CHECK(k_cache.scalar_type() == q.scalar_type() && v_cache.scalar_type() == q.scalar_type(), "gqa_share_sparse_decode: dtype mismatch");
+    TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "gqa_share_sparse_decode: k / v cache shapes differ");
+    TORCH_CHECK(q.stride(2) == 1 && k_cache.stride(3) == 1 && v_cache.stride(3) == 1, "gqa_share_sparse_decode: innermost dimension must be contiguous");
+    const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2), block_size = k_cache.size(1), Hkv = k_cache.size(2), topk = topk_idx.size(2);
+    TORCH_CHECK(k_cache.size(3) == D && Hkv > 0 && Hq % Hkv == 0 && seq_lens.size(0) == B && topk_idx.size(1) == B,
+                "gqa_share_sparse_decode: shape mismatch");
+    TORCH_CHECK(topk_idx.size(0) == Hkv || topk_idx.size(0) == Hq, "gqa_share_sparse_decode: topk_idx must hold one list per kv head or per q head");
+    TORCH_CHECK(is_index(topk_idx) || topk_idx.scalar_type() == at::kShort || topk_idx.scalar_type() == at::kChar || topk_idx.scalar_type() == at::kByte,
+                "gqa_share_sparse_decode: topk_idx must be an integer tensor");
+    TORCH_CHECK(is_index(seq_lens), "gqa_share_sparse_decode: seq_lens must be int32 or int64");
+    const bool direct = req_to_token.has_value();
+    TORCH_CHECK(direct == req_pool_indices.has_value() && direct != block_table.has_value(),
+                "gqa_share_sparse_decode: exactly one of block_table and (req_to_token, req_pool_indices)");
+    int64_t max_kv_len;
+    if (direct) {
+        TORCH_CHECK(req_to_token->dim() == 2 && is_index(*req_to_token) && req_pool_indices->dim() == 1 && is_index(*req_pool_indices) &&
+                        req_pool_indices->size(0) == B && req_pool_indices->is_contiguous(), "gqa_share_sparse_decode: req_to_token / req_pool_indices");
+        TORCH_CHECK(max_num_blocks > 0 && num_pages > 0 && max_num_blocks * block_size <= req_to_token->size(1),
+                    "gqa_share_sparse_decode: max_num_blocks / num_pages");
+        max_kv_len = max_num_blocks * block_size;
+    } else {
+        TORCH_CHECK(block_table->dim() == 2 && is_index(*block_table) && block_table->size(0) == B, "gqa_share_sparse_decode: block_table");
+        max_kv_len = block_table->size(1) * block_size;
+    }
+    max_kv_len = std::min<int64_t>(max_kv_len, INT32_MAX);
+    const at::Tensor lens = seq_lens.scalar_type() == at::kInt && seq_lens.is_contiguous() ? seq_lens : seq_lens.to(at::kInt).contiguous();
+    const at::Tensor idx = (is_index(topk_idx)) ? topk_idx : topk_idx.to(at::kInt);
+    const int64_t idx_sh = idx.stride(0) * (idx.size(0) == Hkv ? 1 : Hq / Hkv);
+    at::Tensor sk;
+    if (sink.has_value()) {
+        TORCH_CHECK(sink->dim() == 2 && sink->size(0) == Hq && sink->size(1) == D, "gqa_share_sparse_decode: sink must be [Hq, D]");
+        sk = sink->scalar_type() == at::kFloat || sink->scalar_type() == q.scalar_type() ? *sink : sink->to(at::kFloat);
+        if (sk.stride(1) != 1) sk = sk.contiguous();
+    }
+    TORCH_CHECK(num_chunks >= 0, "gqa_share_sparse_decode: num_chunks");
+    int chunks = (int)num_chunks;
+    if (chunks == 0) chunks = mi_gqa_sparse_decode_num_chunks((int)B, (int)Hkv, (int)topk);
+    at::Tensor out = at::empty({B, Hq, D}, q.options());
+    const size_t wsb = mi_gqa_sparse_decode_workspace((int)B, (int)Hq, (int)D, chunks);
+    at::Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 16)}, at::dtype(at::kByte).device(q.device()));
+    const at::Tensor *tab = direct ? &*req_to_token : &*block_table;
+    const int rc = mi_gqa_sparse_decode(
+        q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), lens.data_ptr<int>(), idx.data_ptr(), idx.scalar_type() == at::kLong,
+        idx_sh, idx.stride(1), idx.stride(2), direct ? nullptr : tab->data_ptr(), tab->scalar_type() == at::kLong, tab->stride(0), tab->stride(1),
+        direct ? tab->data_ptr() : nullptr, tab->scalar_type() == at::kLong, tab->stride(0), tab->stride(1), direct ? (int)tab->size(1) : 0,
+        direct ? req_pool_indices->data_ptr() : nullptr, direct && req_pool_indices->scalar_type() == at::kLong,
+        sk.defined() ? sk.data_ptr() : nullptr, sk.defined() ? dtype_code3(sk) : 0, sk.defined() ? sk.stride(0) : 0, (int)B, (int)Hq, (int)Hkv, (int)D,
+        (int)block_size, (int)topk, (int)max_kv_len, direct ? (int)num_pages : 1, sanitize_page_ids, q.stride(0), q.stride(1), k_cache.stride(0),
+        k_cache.stride(1), k_cache.stride(2), v_cache.stride(0), v_cache.stride(1), v_cache.stride(2), out.stride(0), out.stride(1), (float)sm_scale,
+        dtype_code(q), chunks, ws.data_ptr(), wsb, cur_stream());
+    TORCH_CHECK(rc == 0, "mi_gqa_sparse_decode failed with code ", rc,
+                " (head_dim a multiple of 8 up to 256, block_size 16 / 32 / 64 / 128, 1 <= num_chunks <= max(1, topk), at most 1024 list slots per chunk)");
+    return out;
+}
+
+// the chunk count gqa_share_sparse_decode picks for num_chunks = 0 (host arithmetic; a power of two)
+int64_t gqa_share_sparse_num_chunks(int64_t batch, int64_t kv_heads, int64_t topk)
+{
+    return mi_gqa_sparse_decode_num_chunks((int)batch, (int)kv_heads, (int)std::min<int64_t>(topk, INT32_MAX));
+}
+
 // SwiGLU + per-row INT8 quantisation; same arguments / returns as swiglu_quant (activation/swiglu_quant.py:87-127).
 std::tuple<at::Tensor, at::Tensor> swiglu_quant(const at::Tensor &x, const at::Tensor &group_list, int64_t group_list_type,
                                                 bool need_quant, bool do_limit, double limit)
@@ -1021,6 +1096,10 @@ TORCH_LIBRARY_FRAGMENT(npu, m)
     m.def("situ_and_mul(Tensor x, Tensor? group_list, int? group_list_type, float beta, float? linear_beta, bool need_quant) -> (Tensor, Tensor)");
     m.def("fia_blockq_sparse_prefill(Tensor q, Tensor k_cache, Tensor v_cache, Tensor topk_idx, Tensor seq_lens, Tensor per_query_req, "
           "Tensor req_to_token, int block_size, float sm_scale, Tensor? block_table_out=None, Tensor? actual_kvlen_out=None) -> Tensor");
+    m.def("gqa_share_sparse_num_chunks", &sglang::npu_kernel::gqa_share_sparse_num_chunks);      // no tensor arguments: catch-all kernel
+    m.def("gqa_share_sparse_decode(Tensor q, Tensor? sink, Tensor k_cache, Tensor v_cache, Tensor? block_table, Tensor seq_lens, Tensor topk_idx, "
+          "float sm_scale, int num_chunks=0, Tensor? req_to_token=None, Tensor? req_pool_indices=None, int max_num_blocks=0, int num_pages=0, "
+          "bool sanitize_page_ids=False) -> Tensor");
     m.def("attn_residual_mix(Tensor prefix_sum, Tensor bank, int num_valid_blocks, Tensor combined_weight, float variance_epsilon) -> Tensor");
     m.def("mul_add(Tensor routed_input, Tensor shared_input, float scaling_factor) -> Tensor");
     m.def("zero_experts_compute_identity(Tensor(a!) expert_indices, Tensor(b!) expert_scales, int num_experts, Tensor hidden_states, "
@@ -1058,6 +1137,7 @@ TORCH_LIBRARY_IMPL(npu, CUDA, m)
     m.impl("swiglu_oai_quant", TORCH_FN(sglang::npu_kernel::swiglu_oai_quant));
     m.impl("situ_and_mul", TORCH_FN(sglang::npu_kernel::situ_and_mul));
     m.impl("fia_blockq_sparse_prefill", TORCH_FN(sglang::npu_kernel::fia_blockq_sparse_prefill));
+    m.impl("gqa_share_sparse_decode", TORCH_FN(sglang::npu_kernel::gqa_share_sparse_decode));
     m.impl("attn_residual_mix", TORCH_FN(sglang::npu_kernel::attn_residual_mix));
     m.impl("mul_add", TORCH_FN(sglang::npu_kernel::mul_add));
     m.impl("zero_experts_compute_identity", TORCH_FN(sglang::npu_kernel::zero_experts_compute_identity));
