@@ -8,6 +8,8 @@
  *   mi_gqa_decode            <- attention/decode_attention.py:233-450,646-760 (decode_gqa, decode_gqa_high_performance)
  *   mi_gqa_decode_sinks      <- attention/sinks_attention.py:7-286 (attention_sinks_triton, attention_sinks_prefill_triton)
  *   mi_gqa_sparse_decode     <- attention/gqa_share_sparse_attention.py:180-878 (flash_decode_bnsd_with_gqa_share_sparse)
+ *   mi_gqa_block_score_topk  <- indexer/flash_block_score_decode.py:97-1029,1571-1889 (flash_decode_bnsd_with_topk_idx, score-only form)
+ *   mi_topk_append_local_block <- indexer/flash_block_score_decode.py:1451-1562 (append_local_block_to_topk_idx)
  *   mi_swiglu_quant          <- activation/swiglu_quant.py:8-127     (_swiglu_quant_kernel / swiglu_quant)
  *   mi_add_rmsnorm_bias      <- norm/add_rmsnorm_bias.py:8-147        (add_rmsnorm_bias_kernel / add_rmsnorm_bias)
  *                               norm/add_rmsnorm_bias.py:150-232      (add_gemma_rms_norm)
@@ -164,6 +166,37 @@ int mi_gqa_sparse_decode(const void *q, const void *k, const void *v, void *out,
                          int64_t k_stride_h, int64_t v_stride_blk, int64_t v_stride_row, int64_t v_stride_h, int64_t o_stride_b,
                          int64_t o_stride_h, float sm_scale, int dtype, int num_chunks, void *workspace, size_t workspace_bytes,
                          void *stream);
+
+/* ---- block-score indexer of the block-sparse decode (indexer/flash_block_score_decode.py:749-1029, 97-527, 1571-1889) ----------------
+ * Produces the topk_idx [q_heads, batch, topk] int32 (contiguous) that mi_gqa_sparse_decode consumes.  Per (b, h), kh = h / group,
+ * len = seq_lens[b] (packed_seq_lens: seq_lens[b * group + h % group]) clamped to [0, min(max_seqblock, bt_cols) * block_size], nb =
+ * ceil(len / block_size): block j < nb scores max_n s (score_lse = 0) or m + log2(sum_n exp2(s - m)) (score_lse = 1; NaN -> -inf) over
+ * s = (q[b,h] . k[page(b,j), n, kh]) * sm_scale * log2(e), keys n with j * block_size + n < len; then j < init_blocks -> 1e30, then
+ * j >= max(0, nb - local_blocks) -> 1e29.  Output: the min(topk, nb) blocks of highest score, descending, ties by ascending block id, then
+ * -1 (never a duplicate, never a block >= nb).  When the largest nb of the group is <= topk nothing is scored: row h is 0 .. nb - 1.
+ * Pages as for mi_gqa_sparse_decode (block_table[b, j], or the request map); K is fetched once per kv head for the group's longest length
+ * and masked per row; rows and table entries wholly behind that length are not read.
+ * append_local_num_blocks > 0: the output is [q_heads, batch, topk + 1]; entries >= append_local_num_blocks become -1 and slot topk holds
+ * min(max(len - 1, 0) / block_size, append_local_num_blocks - 1), or -1 when that block is among the entries -- what
+ * mi_topk_append_local_block makes of the plain output.
+ * LIMITS (MI_SGL_EINVAL beyond them): 1 <= max_seqblock <= 16384 (one row of fp32 scores in 64 KB of LDS); 1 <= topk <= 1024; block_size
+ * 16 / 32 / 64 / 128; head_dim a multiple of 8 up to 256; sm_scale > 0; dtype BF16 / F16.  workspace: mi_gqa_block_score_topk_workspace()
+ * bytes (fp32 scores [batch, q_heads, max_seqblock]; rows keep the natural scores of the blocks j < nb when anything was scored).
+ * Two launches sized from these integers only; nothing is read back: capturable in a graph. */
+size_t mi_gqa_block_score_topk_workspace(int batch, int q_heads, int max_seqblock);
+int mi_gqa_block_score_topk(const void *q, const void *k, int32_t *topk_idx, const int32_t *seq_lens, int packed_seq_lens,
+                            const void *block_table, int block_table_is_i64, int64_t bt_stride_b, int64_t bt_stride_n, int bt_cols,
+                            const void *req_to_token, int req_to_token_is_i64, int64_t rtt_stride_r, int64_t rtt_stride_t, int rtt_cols,
+                            const void *req_pool_indices, int req_pool_is_i64, int batch, int q_heads, int kv_heads, int head_dim,
+                            int block_size, int max_seqblock, int topk, int init_blocks, int local_blocks, int score_lse,
+                            int append_local_num_blocks, int num_pages, int sanitize_page_ids, int64_t q_stride_b, int64_t q_stride_h,
+                            int64_t k_stride_blk, int64_t k_stride_row, int64_t k_stride_h, float sm_scale, int dtype, void *workspace,
+                            size_t workspace_bytes, void *stream);
+/* topk_idx [heads, batch, topk] int32 contiguous -> out [heads, batch, topk + 1]: an entry outside [0, num_blocks) or with
+ * entry * block_size > max(seq_lens[b] - 1, 0) becomes -1; slot topk = min(max(seq_lens[b] - 1, 0) / block_size, num_blocks - 1), or -1
+ * when that block is among the entries kept (an empty sequence yields block 0). */
+int mi_topk_append_local_block(const int32_t *topk_idx, const int32_t *seq_lens, int32_t *out, int heads, int batch, int topk, int block_size,
+                               int num_blocks, void *stream);
 
 /* ---- SwiGLU + per-row INT8 quantisation (swiglu_quant.py:87-127) -------------------------------------------------
  * x [rows, cols] (cols = 2I; gate = x[:, :I], up = x[:, I:]); only the first `total` rows are processed, where total =

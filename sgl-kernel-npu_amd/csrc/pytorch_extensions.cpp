@@ -395,6 +395,76 @@ int64_t gqa_share_sparse_num_chunks(int64_t batch, int64_t kv_heads, int64_t top
     return mi_gqa_sparse_decode_num_chunks((int)batch, (int)kv_heads, (int)std::min<int64_t>(topk, INT32_MAX));
 }
 
+// indexer/flash_block_score_decode.py:1571-1889, score-only form: block scores + top-k selection (csrc/kernels/gqa_block_score.hip).
+// Returns topk_idx [Hq, B, topk] int32, or [Hq, B, topk + 1] with append_local (max_num_blocks > 0 then: the causal-local block's bound).
+// seq_lens [B], or [B * group] with packed_seq_lens; exactly one of block_table and (req_to_token, req_pool_indices, num_pages).
+at::Tensor gqa_block_score_topk(const at::Tensor &q, const at::Tensor &k_cache, const std::optional<at::Tensor> &block_table,
+                                const at::Tensor &seq_lens, int64_t max_seqlen, int64_t topk, int64_t init_blocks, int64_t local_blocks,
+                                double sm_scale, bool score_lse, const std::optional<at::Tensor> &req_to_token,
+                                const std::optional<at::Tensor> &req_pool_indices, int64_t max_num_blocks, int64_t num_pages,
+                                bool sanitize_page_ids, bool packed_seq_lens, bool append_local)
+{
+    const c10::DeviceGuard device_guard(q.device());
+    auto is_index = [](const at::Tensor &t) { return t.scalar_type() == at::kInt || t.scalar_type() == at::kLong; };
+    TORCH_CHECK(q.dim() == 3 && k_cache.dim() == 4 && seq_lens.dim() == 1, "gqa_block_score_topk: q [B, Hq, D], k_cache [pages, block, Hkv, D], seq_lens 1-d");
+    TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "gqa_block_score_topk: q must be fp16 or bf16");
+    TORCH_CHECK(k_cache.scalar_type() == q.scalar_type(), "gqa_block_score_topk: dtype mismatch");
+    TORCH_CHECK(q.stride(2) == 1 && k_cache.stride(3) == 1, "gqa_block_score_topk: innermost dimension must be contiguous");
+    const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2), block_size = k_cache.size(1), Hkv = k_cache.size(2);
+    TORCH_CHECK(k_cache.size(3) == D && Hkv > 0 && Hq % Hkv == 0, "gqa_block_score_topk: shape mismatch");
+    TORCH_CHECK(is_index(seq_lens) && seq_lens.size(0) == (packed_seq_lens ? B * (Hq / Hkv) : B), "gqa_block_score_topk: seq_lens");
+    const bool direct = req_to_token.has_value();
+    TORCH_CHECK(direct == req_pool_indices.has_value() && direct != block_table.has_value(),
+                "gqa_block_score_topk: exactly one of block_table and (req_to_token, req_pool_indices)");
+    if (direct) {
+        TORCH_CHECK(req_to_token->dim() == 2 && is_index(*req_to_token) && req_pool_indices->dim() == 1 && is_index(*req_pool_indices) &&
+                        req_pool_indices->size(0) == B && req_pool_indices->is_contiguous(), "gqa_block_score_topk: req_to_token / req_pool_indices");
+        TORCH_CHECK(num_pages > 0, "gqa_block_score_topk: num_pages");
+    } else {
+        TORCH_CHECK(block_table->dim() == 2 && is_index(*block_table) && block_table->size(0) == B && block_table->size(1) > 0,
+                    "gqa_block_score_topk: block_table");
+    }
+    TORCH_CHECK(block_size > 0 && max_seqlen > 0, "gqa_block_score_topk: max_seqlen");
+    const int64_t max_seqblock = (max_seqlen + block_size - 1) / block_size;
+    TORCH_CHECK(max_seqblock <= 16384, "gqa_block_score_topk: max_seqlen spans ", max_seqblock, " blocks, the limit is 16384");
+    TORCH_CHECK(topk >= 1 && topk <= 1024, "gqa_block_score_topk: topk must lie in [1, 1024]");
+    TORCH_CHECK(init_blocks >= 0 && local_blocks >= 0 && init_blocks <= INT32_MAX && local_blocks <= INT32_MAX, "gqa_block_score_topk: init / local blocks");
+    TORCH_CHECK(!append_local || (max_num_blocks > 0 && max_num_blocks <= INT32_MAX), "gqa_block_score_topk: append_local needs max_num_blocks");
+    const at::Tensor lens = seq_lens.scalar_type() == at::kInt && seq_lens.is_contiguous() ? seq_lens : seq_lens.to(at::kInt).contiguous();
+    at::Tensor out = at::empty({Hq, B, topk + (append_local ? 1 : 0)}, q.options().dtype(at::kInt));
+    const size_t wsb = mi_gqa_block_score_topk_workspace((int)B, (int)Hq, (int)max_seqblock);
+    at::Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 16)}, at::dtype(at::kByte).device(q.device()));
+    const at::Tensor *tab = direct ? &*req_to_token : &*block_table;
+    const int rc = mi_gqa_block_score_topk(
+        q.data_ptr(), k_cache.data_ptr(), out.data_ptr<int>(), lens.data_ptr<int>(), packed_seq_lens, direct ? nullptr : tab->data_ptr(),
+        tab->scalar_type() == at::kLong, tab->stride(0), tab->stride(1), direct ? 0 : (int)std::min<int64_t>(tab->size(1), INT32_MAX),
+        direct ? tab->data_ptr() : nullptr, tab->scalar_type() == at::kLong, tab->stride(0), tab->stride(1),
+        direct ? (int)std::min<int64_t>(tab->size(1), INT32_MAX) : 0, direct ? req_pool_indices->data_ptr() : nullptr,
+        direct && req_pool_indices->scalar_type() == at::kLong, (int)B, (int)Hq, (int)Hkv, (int)D, (int)block_size, (int)max_seqblock, (int)topk,
+        (int)init_blocks, (int)local_blocks, score_lse, append_local ? (int)max_num_blocks : 0, direct ? (int)num_pages : 1, sanitize_page_ids,
+        q.stride(0), q.stride(1), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), (float)sm_scale, dtype_code(q), ws.data_ptr(), wsb,
+        cur_stream());
+    TORCH_CHECK(rc == 0, "mi_gqa_block_score_topk failed with code ", rc,
+                " (head_dim a multiple of 8 up to 256, block_size 16 / 32 / 64 / 128, sm_scale > 0, strides multiples of 8 elements)");
+    return out;
+}
+
+// indexer/flash_block_score_decode.py:1519-1562: [H, B, topk] int32 -> [H, B, topk + 1] with the causal-local block appended
+at::Tensor topk_append_local_block(const at::Tensor &topk_idx, const at::Tensor &seq_lens, int64_t block_size, int64_t num_blocks)
+{
+    const c10::DeviceGuard device_guard(topk_idx.device());
+    TORCH_CHECK(topk_idx.dim() == 3 && topk_idx.scalar_type() == at::kInt && topk_idx.is_contiguous(), "topk_append_local_block: topk_idx [H, B, topk] int32, contiguous");
+    TORCH_CHECK(seq_lens.dim() == 1 && seq_lens.size(0) == topk_idx.size(1) && (seq_lens.scalar_type() == at::kInt || seq_lens.scalar_type() == at::kLong),
+                "topk_append_local_block: seq_lens [B], int32 or int64");
+    TORCH_CHECK(block_size > 0 && block_size <= INT32_MAX && num_blocks > 0 && num_blocks <= INT32_MAX, "topk_append_local_block: block_size / num_blocks");
+    const at::Tensor lens = seq_lens.scalar_type() == at::kInt && seq_lens.is_contiguous() ? seq_lens : seq_lens.to(at::kInt).contiguous();
+    at::Tensor out = at::empty({topk_idx.size(0), topk_idx.size(1), topk_idx.size(2) + 1}, topk_idx.options());
+    const int rc = mi_topk_append_local_block(topk_idx.data_ptr<int>(), lens.data_ptr<int>(), out.data_ptr<int>(), (int)topk_idx.size(0),
+                                              (int)topk_idx.size(1), (int)topk_idx.size(2), (int)block_size, (int)num_blocks, cur_stream());
+    TORCH_CHECK(rc == 0, "mi_topk_append_local_block failed with code ", rc);
+    return out;
+}
+
 // SwiGLU + per-row INT8 quantisation; same arguments / returns as swiglu_quant (activation/swiglu_quant.py:87-127).
 std::tuple<at::Tensor, at::Tensor> swiglu_quant(const at::Tensor &x, const at::Tensor &group_list, int64_t group_list_type,
                                                 bool need_quant, bool do_limit, double limit)
@@ -1100,6 +1170,10 @@ TORCH_LIBRARY_FRAGMENT(npu, m)
     m.def("gqa_share_sparse_decode(Tensor q, Tensor? sink, Tensor k_cache, Tensor v_cache, Tensor? block_table, Tensor seq_lens, Tensor topk_idx, "
           "float sm_scale, int num_chunks=0, Tensor? req_to_token=None, Tensor? req_pool_indices=None, int max_num_blocks=0, int num_pages=0, "
           "bool sanitize_page_ids=False) -> Tensor");
+    m.def("gqa_block_score_topk(Tensor q, Tensor k_cache, Tensor? block_table, Tensor seq_lens, int max_seqlen, int topk, int init_blocks, "
+          "int local_blocks, float sm_scale, bool score_lse=False, Tensor? req_to_token=None, Tensor? req_pool_indices=None, int max_num_blocks=0, "
+          "int num_pages=0, bool sanitize_page_ids=False, bool packed_seq_lens=False, bool append_local=False) -> Tensor");
+    m.def("topk_append_local_block(Tensor topk_idx, Tensor seq_lens, int block_size, int num_blocks) -> Tensor");
     m.def("attn_residual_mix(Tensor prefix_sum, Tensor bank, int num_valid_blocks, Tensor combined_weight, float variance_epsilon) -> Tensor");
     m.def("mul_add(Tensor routed_input, Tensor shared_input, float scaling_factor) -> Tensor");
     m.def("zero_experts_compute_identity(Tensor(a!) expert_indices, Tensor(b!) expert_scales, int num_experts, Tensor hidden_states, "
@@ -1138,6 +1212,8 @@ TORCH_LIBRARY_IMPL(npu, CUDA, m)
     m.impl("situ_and_mul", TORCH_FN(sglang::npu_kernel::situ_and_mul));
     m.impl("fia_blockq_sparse_prefill", TORCH_FN(sglang::npu_kernel::fia_blockq_sparse_prefill));
     m.impl("gqa_share_sparse_decode", TORCH_FN(sglang::npu_kernel::gqa_share_sparse_decode));
+    m.impl("gqa_block_score_topk", TORCH_FN(sglang::npu_kernel::gqa_block_score_topk));
+    m.impl("topk_append_local_block", TORCH_FN(sglang::npu_kernel::topk_append_local_block));
     m.impl("attn_residual_mix", TORCH_FN(sglang::npu_kernel::attn_residual_mix));
     m.impl("mul_add", TORCH_FN(sglang::npu_kernel::mul_add));
     m.impl("zero_experts_compute_identity", TORCH_FN(sglang::npu_kernel::zero_experts_compute_identity));

@@ -4,7 +4,7 @@ python/sgl_kernel_npu/sgl_kernel_npu/attention/gqa_share_sparse_attention.py:635
 The decode half of the block-sparse attention whose prefill half is `flash_prefill_bnsd_blockq_sparse_fia`: every sequence attends to the
 KV blocks its list names (logical block ids, -1 = none, anywhere in the list), per KV head, with an optional vector sink per q head.
 One HIP launch (csrc/kernels/gqa_sparse_decode.hip) per chunk count of 1, plus a merge launch for more; the chunk count is chosen from
-shapes only, so the op can be captured in a graph.  The indexer that produces `topk_idx` is not part of this package.  No reference test
+shapes only, so the op can be captured in a graph.  The indexer that produces `topk_idx` is `indexer.flash_block_score_decode.flash_decode_bnsd_with_topk_idx`.  No reference test
 exists for this file (parity is pinned by outputs of the reference kernel stored under tests/golden/)."""
 from __future__ import annotations
 
