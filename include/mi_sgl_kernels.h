@@ -10,6 +10,8 @@
  *   mi_gqa_sparse_decode     <- attention/gqa_share_sparse_attention.py:180-878 (flash_decode_bnsd_with_gqa_share_sparse)
  *   mi_gqa_block_score_topk  <- indexer/flash_block_score_decode.py:97-1029,1571-1889 (flash_decode_bnsd_with_topk_idx, score-only form)
  *   mi_topk_append_local_block <- indexer/flash_block_score_decode.py:1451-1562 (append_local_block_to_topk_idx)
+ *   mi_gqa_prefill_block_score, mi_prefill_topk_from_score <- indexer/flash_block_score_prefill.py:21-220,434-557,673-811,865-909
+ *                               (flash_prefill_bnsd_score, flash_prefill_bnsd_topk_from_score, flash_prefill_bnsd_with_topk_idx)
  *   mi_swiglu_quant          <- activation/swiglu_quant.py:8-127     (_swiglu_quant_kernel / swiglu_quant)
  *   mi_add_rmsnorm_bias      <- norm/add_rmsnorm_bias.py:8-147        (add_rmsnorm_bias_kernel / add_rmsnorm_bias)
  *                               norm/add_rmsnorm_bias.py:150-232      (add_gemma_rms_norm)
@@ -197,6 +199,35 @@ int mi_gqa_block_score_topk(const void *q, const void *k, int32_t *topk_idx, con
  * when that block is among the entries kept (an empty sequence yields block 0). */
 int mi_topk_append_local_block(const int32_t *topk_idx, const int32_t *seq_lens, int32_t *out, int heads, int batch, int topk, int block_size,
                                int num_blocks, void *stream);
+
+/* ---- block-score indexer of the block-sparse prefill (indexer/flash_block_score_prefill.py:21-220, 434-557, 673-811, 865-909) ----------
+ * mi_gqa_prefill_block_score writes EVERY element of score [idx_heads, total_q, max_seqblock] fp32 (strides s_stride_h, s_stride_t, 1).
+ * Request r owns the tokens t in [cu_seqlens[r], cu_seqlens[r + 1]); L = seq_lens[r] clamped to [0, max_seqblock * block_size]; the page of
+ * its logical block j is req_to_token[req_pool_indices[r], min(j * block_size, rtt_cols - 1)] / block_size.  Key n of block j is visible to
+ * token t iff j * block_size + n < L and j * block_size + n <= pos(t), where pos(t) = query_pos[t] when query_pos is given and the token's
+ * true position seq_lens[r] - (cu_seqlens[r + 1] - cu_seqlens[r]) + (t - cu_seqlens[r]) otherwise (the reference kernel compares with the
+ * PACKED index t itself: pass query_pos[t] = t for that).  score[h, t, j] over the visible keys of block j: max_n s (score_lse = 0) or
+ * m + log2(sum_n exp2(s - m)) (score_lse = 1), s = (q[t, h] . k[page, n, h / group]) * sm_scale * log2(e); -inf when no key is visible, for
+ * tokens at or behind cu_seqlens[num_reqs] and for a negative position.  Blocks wholly behind a tile's last position are neither looked up
+ * nor loaded.  cu_seqlens [num_reqs + 1] (ascending from 0), seq_lens / req_pool_indices [num_reqs], query_pos [total_q]: int32 or int64.
+ * mi_prefill_topk_from_score selects per row of score [heads, total_q, max_seqblock] (any strides).  fused = 0: out [heads, total_q, topk] =
+ * the min(topk, #scores above -inf) best blocks, descending score, ties by ascending block id, then -1.  fused = 1 (per_query_seq_lens
+ * [total_q], the causal length of every token, required): out [heads, total_q, topk + 1]; of those entries the ones with block *
+ * block_size > max(len_t - 1, 0) become -1 IN PLACE, and slot topk holds min(max(len_t - 1, 0) / block_size, max_seqblock - 1), or -1 when
+ * that block is among the entries kept -- flash_prefill_bnsd_topk_from_score bit for bit.
+ * LIMITS (MI_SGL_EINVAL beyond them): block_size 16 / 32 / 64 / 128; head_dim a multiple of 8 up to 256; 1 <= max_seqblock <= 16384;
+ * 1 <= topk <= 1024; sm_scale > 0; dtype BF16 / F16; q / k strides multiples of 8 elements.  No workspace.  One launch each, sized from these
+ * integers only; nothing is read back: capturable in a graph. */
+int mi_gqa_prefill_block_score(const void *q, const void *k, float *score, const void *cu_seqlens, int cu_seqlens_is_i64, const void *seq_lens,
+                               int seq_lens_is_i64, const void *req_to_token, int req_to_token_is_i64, int64_t rtt_stride_r,
+                               int64_t rtt_stride_t, int rtt_cols, const void *req_pool_indices, int req_pool_is_i64, const void *query_pos,
+                               int query_pos_is_i64, int total_q, int num_reqs, int idx_heads, int kv_heads, int head_dim, int block_size,
+                               int max_seqblock, int score_lse, int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_blk,
+                               int64_t k_stride_row, int64_t k_stride_h, int64_t s_stride_h, int64_t s_stride_t, float sm_scale, int dtype,
+                               void *stream);
+int mi_prefill_topk_from_score(const float *score, int64_t s_stride_h, int64_t s_stride_t, int64_t s_stride_k, const void *per_query_seq_lens,
+                               int per_query_seq_lens_is_i64, int32_t *topk_idx, int heads, int total_q, int max_seqblock, int topk,
+                               int block_size, int fused, void *stream);
 
 /* ---- SwiGLU + per-row INT8 quantisation (swiglu_quant.py:87-127) -------------------------------------------------
  * x [rows, cols] (cols = 2I; gate = x[:, :I], up = x[:, I:]); only the first `total` rows are processed, where total =

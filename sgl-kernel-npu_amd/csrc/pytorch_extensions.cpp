@@ -465,6 +465,75 @@ at::Tensor topk_append_local_block(const at::Tensor &topk_idx, const at::Tensor 
     return out;
 }
 
+// indexer/flash_block_score_prefill.py:434-557: block scores of every query token of a prefill chunk (csrc/kernels/gqa_block_score_prefill.hip).
+// Returns score [Hidx, total_q, ceil(max_seqlen / block)] fp32, every element written.  query_pos [total_q]: the position each token's causal
+// mask compares with; absent = the token's true position seq_lens[r] - q_len[r] + i.
+at::Tensor gqa_prefill_block_score(const at::Tensor &q, const at::Tensor &k_cache, const at::Tensor &cu_seqlens, const at::Tensor &seq_lens,
+                                   const at::Tensor &req_to_token, const at::Tensor &req_pool_indices, int64_t max_seqlen, double sm_scale,
+                                   bool score_lse, const std::optional<at::Tensor> &query_pos)
+{
+    const c10::DeviceGuard device_guard(q.device());
+    auto is_index = [](const at::Tensor &t) { return t.scalar_type() == at::kInt || t.scalar_type() == at::kLong; };
+    TORCH_CHECK(q.dim() == 3 && k_cache.dim() == 4, "gqa_prefill_block_score: q [total_q, Hidx, D], k_cache [pages, block, Hkv, D]");
+    TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "gqa_prefill_block_score: q must be fp16 or bf16");
+    TORCH_CHECK(k_cache.scalar_type() == q.scalar_type(), "gqa_prefill_block_score: dtype mismatch");
+    TORCH_CHECK(q.stride(2) == 1 && k_cache.stride(3) == 1, "gqa_prefill_block_score: innermost dimension must be contiguous");
+    const int64_t total_q = q.size(0), Hidx = q.size(1), D = q.size(2), block_size = k_cache.size(1), Hkv = k_cache.size(2);
+    TORCH_CHECK(k_cache.size(3) == D && Hkv > 0 && Hidx > 0 && Hidx % Hkv == 0, "gqa_prefill_block_score: shape mismatch");
+    TORCH_CHECK(total_q <= INT32_MAX, "gqa_prefill_block_score: total_q");
+    TORCH_CHECK(cu_seqlens.dim() == 1 && is_index(cu_seqlens) && cu_seqlens.size(0) >= 1 && cu_seqlens.is_contiguous(), "gqa_prefill_block_score: cu_seqlens");
+    const int64_t n = cu_seqlens.size(0) - 1;
+    TORCH_CHECK(seq_lens.dim() == 1 && is_index(seq_lens) && seq_lens.size(0) == n && seq_lens.is_contiguous(), "gqa_prefill_block_score: seq_lens [n]");
+    TORCH_CHECK(req_pool_indices.dim() == 1 && is_index(req_pool_indices) && req_pool_indices.size(0) == n && req_pool_indices.is_contiguous(),
+                "gqa_prefill_block_score: req_pool_indices [n]");
+    TORCH_CHECK(req_to_token.dim() == 2 && is_index(req_to_token) && req_to_token.size(1) > 0, "gqa_prefill_block_score: req_to_token [requests, columns]");
+    if (query_pos.has_value())
+        TORCH_CHECK(query_pos->dim() == 1 && is_index(*query_pos) && query_pos->size(0) == total_q && query_pos->is_contiguous(),
+                    "gqa_prefill_block_score: query_pos [total_q]");
+    TORCH_CHECK(block_size > 0 && max_seqlen > 0, "gqa_prefill_block_score: max_seqlen");
+    const int64_t max_seqblock = (max_seqlen + block_size - 1) / block_size;
+    TORCH_CHECK(max_seqblock <= 16384, "gqa_prefill_block_score: max_seqlen spans ", max_seqblock, " blocks, the limit is 16384");
+    at::Tensor score = at::empty({Hidx, total_q, max_seqblock}, q.options().dtype(at::kFloat));
+    const int rc = mi_gqa_prefill_block_score(
+        q.data_ptr(), k_cache.data_ptr(), score.data_ptr<float>(), cu_seqlens.data_ptr(), cu_seqlens.scalar_type() == at::kLong, seq_lens.data_ptr(),
+        seq_lens.scalar_type() == at::kLong, req_to_token.data_ptr(), req_to_token.scalar_type() == at::kLong, req_to_token.stride(0),
+        req_to_token.stride(1), (int)std::min<int64_t>(req_to_token.size(1), INT32_MAX), req_pool_indices.data_ptr(),
+        req_pool_indices.scalar_type() == at::kLong, query_pos.has_value() ? query_pos->data_ptr() : nullptr,
+        query_pos.has_value() && query_pos->scalar_type() == at::kLong, (int)total_q, (int)n, (int)Hidx, (int)Hkv, (int)D, (int)block_size,
+        (int)max_seqblock, score_lse, q.stride(0), q.stride(1), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), score.stride(0),
+        score.stride(1), (float)sm_scale, dtype_code(q), cur_stream());
+    TORCH_CHECK(rc == 0, "mi_gqa_prefill_block_score failed with code ", rc,
+                " (head_dim a multiple of 8 up to 256, block_size 16 / 32 / 64 / 128, sm_scale > 0, strides multiples of 8 elements)");
+    return score;
+}
+
+// indexer/flash_block_score_prefill.py:761-811 (fused) and the torch.topk branch of :895-909 (not fused): score [H, total_q, blocks] fp32 ->
+// topk_idx [H, total_q, topk (+ 1 fused)] int32
+at::Tensor prefill_topk_from_score(const at::Tensor &score, const std::optional<at::Tensor> &per_query_seq_lens, int64_t topk, int64_t block_size,
+                                   bool fused)
+{
+    const c10::DeviceGuard device_guard(score.device());
+    TORCH_CHECK(score.dim() == 3 && score.scalar_type() == at::kFloat, "prefill_topk_from_score: score [H, total_q, blocks] fp32");
+    TORCH_CHECK(score.size(2) >= 1 && score.size(2) <= 16384, "prefill_topk_from_score: 1 .. 16384 blocks are served");
+    TORCH_CHECK(topk >= 1 && topk <= 1024, "prefill_topk_from_score: topk must lie in [1, 1024]");
+    TORCH_CHECK(block_size > 0 && block_size <= INT32_MAX && score.size(1) <= INT32_MAX && score.size(0) <= INT32_MAX, "prefill_topk_from_score: sizes");
+    TORCH_CHECK(!fused || per_query_seq_lens.has_value(), "prefill_topk_from_score: the fused form needs per_query_seq_lens");
+    const void *lens = nullptr;
+    bool lens_i64 = false;
+    if (fused) {
+        const at::Tensor &l = *per_query_seq_lens;
+        TORCH_CHECK(l.dim() == 1 && l.size(0) == score.size(1) && l.is_contiguous() && (l.scalar_type() == at::kInt || l.scalar_type() == at::kLong),
+                    "prefill_topk_from_score: per_query_seq_lens [total_q], int32 or int64");
+        lens = l.data_ptr(), lens_i64 = l.scalar_type() == at::kLong;
+    }
+    at::Tensor out = at::empty({score.size(0), score.size(1), topk + (fused ? 1 : 0)}, score.options().dtype(at::kInt));
+    const int rc = mi_prefill_topk_from_score(score.data_ptr<float>(), score.stride(0), score.stride(1), score.stride(2), lens, lens_i64,
+                                              out.data_ptr<int>(), (int)score.size(0), (int)score.size(1), (int)score.size(2), (int)topk,
+                                              (int)block_size, fused, cur_stream());
+    TORCH_CHECK(rc == 0, "mi_prefill_topk_from_score failed with code ", rc);
+    return out;
+}
+
 // SwiGLU + per-row INT8 quantisation; same arguments / returns as swiglu_quant (activation/swiglu_quant.py:87-127).
 std::tuple<at::Tensor, at::Tensor> swiglu_quant(const at::Tensor &x, const at::Tensor &group_list, int64_t group_list_type,
                                                 bool need_quant, bool do_limit, double limit)
@@ -1174,6 +1243,9 @@ TORCH_LIBRARY_FRAGMENT(npu, m)
           "int local_blocks, float sm_scale, bool score_lse=False, Tensor? req_to_token=None, Tensor? req_pool_indices=None, int max_num_blocks=0, "
           "int num_pages=0, bool sanitize_page_ids=False, bool packed_seq_lens=False, bool append_local=False) -> Tensor");
     m.def("topk_append_local_block(Tensor topk_idx, Tensor seq_lens, int block_size, int num_blocks) -> Tensor");
+    m.def("gqa_prefill_block_score(Tensor q, Tensor k_cache, Tensor cu_seqlens, Tensor seq_lens, Tensor req_to_token, Tensor req_pool_indices, "
+          "int max_seqlen, float sm_scale, bool lse, Tensor? query_pos=None) -> Tensor");
+    m.def("prefill_topk_from_score(Tensor score, Tensor? per_query_seq_lens, int topk, int block_size, bool fused) -> Tensor");
     m.def("attn_residual_mix(Tensor prefix_sum, Tensor bank, int num_valid_blocks, Tensor combined_weight, float variance_epsilon) -> Tensor");
     m.def("mul_add(Tensor routed_input, Tensor shared_input, float scaling_factor) -> Tensor");
     m.def("zero_experts_compute_identity(Tensor(a!) expert_indices, Tensor(b!) expert_scales, int num_experts, Tensor hidden_states, "
@@ -1214,6 +1286,8 @@ TORCH_LIBRARY_IMPL(npu, CUDA, m)
     m.impl("gqa_share_sparse_decode", TORCH_FN(sglang::npu_kernel::gqa_share_sparse_decode));
     m.impl("gqa_block_score_topk", TORCH_FN(sglang::npu_kernel::gqa_block_score_topk));
     m.impl("topk_append_local_block", TORCH_FN(sglang::npu_kernel::topk_append_local_block));
+    m.impl("gqa_prefill_block_score", TORCH_FN(sglang::npu_kernel::gqa_prefill_block_score));
+    m.impl("prefill_topk_from_score", TORCH_FN(sglang::npu_kernel::prefill_topk_from_score));
     m.impl("attn_residual_mix", TORCH_FN(sglang::npu_kernel::attn_residual_mix));
     m.impl("mul_add", TORCH_FN(sglang::npu_kernel::mul_add));
     m.impl("zero_experts_compute_identity", TORCH_FN(sglang::npu_kernel::zero_experts_compute_identity));
