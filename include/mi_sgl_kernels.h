@@ -229,6 +229,48 @@ int mi_prefill_topk_from_score(const float *score, int64_t s_stride_h, int64_t s
                                int per_query_seq_lens_is_i64, int32_t *topk_idx, int heads, int total_q, int max_seqblock, int topk,
                                int block_size, int fused, void *stream);
 
+/* ---- lightning indexer of DeepSeek-V3.2 (csrc/lightning_indexer/: torch.ops.npu.lightning_indexer) ---------------------------------------
+ * Per query row (token) with index-query Q [64, head_dim 128] and weights w [64], over the keys K [S2, 128] of its sequence:
+ * score[j] = sum_h w[h] * max(0, Q[h] . K[j]) in fp32; sparse_indices row = the n = min(sparse_count, visible) visible keys of highest
+ * score, descending, ties by ascending key, then -1.  Rows: layout_query BSND: query [batch, s1, 64, 128] (strides q_stride_0, q_stride_1,
+ * q_stride_h, 1), rows = batch * s1, act_s1 = actual_seq_lengths_query[b] clamped to [0, s1] (NULL: s1), rows at or behind it see nothing;
+ * TND: query [rows, 64, 128] (q_stride_0 per row, q_stride_1 unused), actual_seq_lengths_query [batch] = prefix sums of the sequences'
+ * row counts, searched on the device; rows at or behind the last prefix sum see nothing.  weights [.., 64] with the same leading layout
+ * (w_stride_0, w_stride_1; heads contiguous).  Keys: layout_key PA_BSND: key [pages, block_size, 1, 128] (k_stride_blk, k_stride_row),
+ * block_table [batch, columns] int32 (bt_stride_b), s2_capacity = columns * block_size, act_s2 = actual_seq_lengths_key[b]; BSND: key
+ * [batch, s2_capacity, 1, 128] (k_stride_blk per sequence), act_s2 = actual_seq_lengths_key[b] (NULL: s2_capacity); TND: key
+ * [s2_capacity, 1, 128] with actual_seq_lengths_key [batch] = prefix sums (sequence b owns key rows [sum[b - 1], sum[b])).  act_s2 is
+ * clamped to [0, s2_capacity].  visible = act_s2 (sparse_mode 0) or, sparse_mode 3, act_s2 - (act_s1 - 1 - r) for row r of its sequence,
+ * clamped to [0, act_s2].  Keys at or behind a workgroup's largest visible count, and their table entries, are never read.
+ * mi_lightning_indexer_score writes the fp32 scores alone: scores [rows, score_stride], score_stride >= s2_capacity rounded up to a
+ * multiple of 64.  Of a row with visible > 0, positions below visible hold the score; a position at or behind visible holds -inf
+ * (inside a stage of keys its group computed) or is untouched; rows with visible = 0 are untouched.  The select reads [0, visible) only.
+ * workspace: mi_lightning_indexer_workspace() bytes, at most 256 MiB (or the positive byte count in the environment variable
+ * MI_LIGHTNING_INDEXER_WS_BYTES) unless four rows need more: mi_lightning_indexer runs larger inputs in slices of rows, each a score and a
+ * select launch.  All launches are sized from these integers only; nothing is read back: capturable in a graph.
+ * LIMITS (MI_SGL_EINVAL beyond them): heads = 64, key_heads = 1, head_dim = 128; dtype BF16 / F16 (query, key, weights alike);
+ * 1 <= sparse_count <= 2048; sparse_mode 0 / 3; block_size a multiple of 16 in [16, 1024]; 1 <= s2_capacity <=
+ * MI_LIGHTNING_INDEXER_MAX_KEYS; a non-paged layout_key equals layout_query; strides of query / key multiples of 8, of weights of 4. */
+#define MI_LIGHTNING_INDEXER_MAX_KEYS 262144
+#define MI_LI_QUERY_BSND 0
+#define MI_LI_QUERY_TND 1
+#define MI_LI_KEY_BSND 0
+#define MI_LI_KEY_TND 1
+#define MI_LI_KEY_PA_BSND 2
+size_t mi_lightning_indexer_workspace(int layout_query, int batch, int s1, int64_t rows, int64_t s2_capacity);
+int mi_lightning_indexer_score(const void *query, const void *key, const void *weights, float *scores, int64_t score_stride,
+                               const int32_t *actual_seq_lengths_query, const int32_t *actual_seq_lengths_key, const int32_t *block_table,
+                               int layout_query, int layout_key, int batch, int s1, int64_t rows, int heads, int key_heads, int head_dim,
+                               int64_t s2_capacity, int block_size, int64_t bt_stride_b, int64_t q_stride_0, int64_t q_stride_1,
+                               int64_t q_stride_h, int64_t w_stride_0, int64_t w_stride_1, int64_t k_stride_blk, int64_t k_stride_row,
+                               int sparse_mode, int dtype, void *stream);
+int mi_lightning_indexer(const void *query, const void *key, const void *weights, int32_t *sparse_indices,
+                         const int32_t *actual_seq_lengths_query, const int32_t *actual_seq_lengths_key, const int32_t *block_table,
+                         int layout_query, int layout_key, int batch, int s1, int64_t rows, int heads, int key_heads, int head_dim,
+                         int64_t s2_capacity, int block_size, int64_t bt_stride_b, int64_t q_stride_0, int64_t q_stride_1, int64_t q_stride_h,
+                         int64_t w_stride_0, int64_t w_stride_1, int64_t k_stride_blk, int64_t k_stride_row, int sparse_count, int sparse_mode,
+                         int dtype, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- SwiGLU + per-row INT8 quantisation (swiglu_quant.py:87-127) -------------------------------------------------
  * x [rows, cols] (cols = 2I; gate = x[:, :I], up = x[:, I:]); only the first `total` rows are processed, where total =
  * group_list[num_groups-1] (group_list_type 0, cumulative) or sum(group_list) (type 1, counts), read on the device.

@@ -534,6 +534,103 @@ at::Tensor prefill_topk_from_score(const at::Tensor &score, const std::optional<
     return out;
 }
 
+// csrc/lightning_indexer/op_host/lightning_indexer.cpp:61-169 (checks: op_host/tiling/lightning_indexer_tiling.cpp:111-479, whose wording the
+// messages keep): the token-level top-k indexer of DeepSeek-V3.2 (csrc/kernels/lightning_indexer.hip).  Defaults as the reference's op
+// definition: layout_query "TND", layout_key "PA_BSND", sparse_count 2048, sparse_mode 3.  Returns sparse_indices int32,
+// [B, S1, 1, sparse_count] (BSND) or [T, 1, sparse_count] (TND): the visible keys of highest score, descending, then -1.
+at::Tensor lightning_indexer(const at::Tensor &query, const at::Tensor &key, const at::Tensor &weights,
+                             const std::optional<at::Tensor> &actual_seq_lengths_query, const std::optional<at::Tensor> &actual_seq_lengths_key,
+                             const std::optional<at::Tensor> &block_table, std::optional<c10::string_view> layout_query,
+                             std::optional<c10::string_view> layout_key, std::optional<int64_t> sparse_count, std::optional<int64_t> sparse_mode)
+{
+    const c10::DeviceGuard device_guard(query.device());   // launches and the current stream follow the tensor's GPU
+    const std::string lq(layout_query.value_or("TND")), lk(layout_key.value_or("PA_BSND"));
+    const int64_t count = sparse_count.value_or(2048), mode = sparse_mode.value_or(3);
+    TORCH_CHECK(lk == "PA_BSND" || lq == lk, "lightning_indexer: under non-PA conditions, layout_query and layout_key should be equal.");
+    TORCH_CHECK(lk == "PA_BSND" || lk == "BSND" || lk == "TND", "lightning_indexer: input attr layout_key only supported PA_BSND, BSND or TND");
+    TORCH_CHECK(lq == "BSND" || lq == "TND", "lightning_indexer: input attr layout_query only supported BSND or TND");
+    TORCH_CHECK(count > 0 && count <= 2048, "lightning_indexer: input attr sparse_count must > 0 and <= 2048.");
+    TORCH_CHECK(mode == 0 || mode == 3, "lightning_indexer: input attr sparse_mode only supported 0 or 3.");
+    TORCH_CHECK(query.scalar_type() == key.scalar_type() && key.scalar_type() == weights.scalar_type(),
+                "lightning_indexer: The data types of the input query, key, and weights must be the same.");
+    TORCH_CHECK(query.scalar_type() == at::kHalf || query.scalar_type() == at::kBFloat16,
+                "lightning_indexer: The data types of the input query, key, and weights must be float16 or bfloat16.");
+    const bool q_tnd = lq == "TND", paged = lk == "PA_BSND", k_tnd = lk == "TND";
+    auto int32_1d = [](const std::optional<at::Tensor> &t) { return !t.has_value() || t->scalar_type() == at::kInt; };
+    if (paged) {
+        TORCH_CHECK(block_table.has_value(), "lightning_indexer: key layout only supported PA_BSND, input block_table must not be null");
+        TORCH_CHECK(actual_seq_lengths_key.has_value(),
+                    "lightning_indexer: key layout only supported PA_BSND, input actual_seq_lengths_key must not be null");
+        TORCH_CHECK(block_table->scalar_type() == at::kInt, "lightning_indexer: input block_table data type only support int32");
+    } else {
+        TORCH_CHECK(!k_tnd || actual_seq_lengths_key.has_value(),
+                    "lightning_indexer: when layout_key is TND, input actual_seq_lengths_key must not be null");
+        TORCH_CHECK(!block_table.has_value(), "lightning_indexer: when key layout is not PA_BSND, input block_table must be null");
+    }
+    TORCH_CHECK(int32_1d(actual_seq_lengths_key), "lightning_indexer: input actual_seq_lengths_key data type only support int32");
+    TORCH_CHECK(!q_tnd || actual_seq_lengths_query.has_value(),
+                "lightning_indexer: when layout_query is TND, input actual_seq_lengths_query must not be null");
+    TORCH_CHECK(int32_1d(actual_seq_lengths_query), "lightning_indexer: input actual_seq_lengths_query data type only support int32");
+    TORCH_CHECK(!block_table.has_value() || block_table->dim() == 2, "lightning_indexer: the dim num of block_table's shape should be 2");
+    const int64_t qd = q_tnd ? 3 : 4, kd = k_tnd ? 3 : 4;
+    TORCH_CHECK(key.dim() == kd, "lightning_indexer: the dim num of key's shape should be ", kd, ", but now is ", key.dim());
+    TORCH_CHECK(query.dim() == qd, "lightning_indexer: the dim num of query's shape should be ", qd, ", but now is ", query.dim());
+    TORCH_CHECK(weights.dim() == qd - 1, "lightning_indexer: the dim num of weights's shape should be ", qd - 1, ", but now is ", weights.dim());
+    for (int64_t i = 0; i < query.dim(); ++i)
+        TORCH_CHECK(query.size(i) > 0, "All values within query's shape should be greater than 0, but shape[", i, "] is ", query.size(i));
+    const int64_t n1 = query.size(qd - 2), D = query.size(qd - 1), n2 = key.size(k_tnd ? 1 : 2);
+    TORCH_CHECK(n2 == 1, "lightning_indexer: key shape", k_tnd ? 1 : 2, " is numhead, only support 1.");
+    TORCH_CHECK(n1 / n2 == 64 && n1 % n2 == 0, "lightning_indexer: N1 is ", n1, ", N2 is ", n2, ", N1 divided by N2 must equal 64.");
+    TORCH_CHECK(D == 128, "lightning_indexer: input query's last dim head_dim only support 128.");
+    TORCH_CHECK(key.size(kd - 1) == D, "lightning_indexer: input query, key shape last dim must be same.");
+    TORCH_CHECK(weights.size(qd - 2) == n1, "lightning_indexer: input query, weight shape dim N1 must be same.");
+    const int64_t B = q_tnd ? actual_seq_lengths_query->numel() : query.size(0), S1 = q_tnd ? 1 : query.size(1);
+    const int64_t rows = q_tnd ? query.size(0) : B * S1;
+    TORCH_CHECK(B > 0 && B <= INT32_MAX && S1 <= INT32_MAX, "lightning_indexer: batch size");
+    if (q_tnd) {
+        TORCH_CHECK(weights.size(0) == rows, "lightning_indexer: TND case input query, weights dim 0 must be same.");
+    } else {
+        TORCH_CHECK(weights.size(0) == B && weights.size(1) == S1, "lightning_indexer: BSND case input query, weight dim 0 and dim 1 must be same.");
+        TORCH_CHECK(!actual_seq_lengths_query.has_value() || actual_seq_lengths_query->numel() == B,
+                    "lightning_indexer: BSND case input query, actual_seq_lengths_query dim 0 must be same");
+    }
+    TORCH_CHECK(!actual_seq_lengths_key.has_value() || actual_seq_lengths_key->numel() == B,
+                "lightning_indexer: input actual_seq_lengths_query, actual_seq_lengths_key dim 0 must be same.");
+    TORCH_CHECK(!block_table.has_value() || block_table->size(0) == B, "lightning_indexer: input block_table dim 0 must be the batch size.");
+    int64_t block_size = 0, cap;
+    if (paged) {
+        block_size = key.size(1);
+        TORCH_CHECK(block_size % 16 == 0 && block_size > 0 && block_size <= 1024,
+                    "lightning_indexer: input key's block_size must be a multiple of 16 and belong to (0, 1024].");
+        TORCH_CHECK(key.size(0) != 0, "lightning_indexer: input key's block_count cannot be 0.");
+        TORCH_CHECK(block_table->size(1) > 0, "lightning_indexer: block_table needs at least one column");
+        cap = block_table->size(1) * block_size;
+    } else {
+        cap = k_tnd ? key.size(0) : key.size(1);
+        TORCH_CHECK(k_tnd || key.size(0) == B, "lightning_indexer: BSND case input query, key dim 0 must be same.");
+    }
+    TORCH_CHECK(cap >= 1 && cap <= MI_LIGHTNING_INDEXER_MAX_KEYS, "lightning_indexer: a sequence may hold up to ", MI_LIGHTNING_INDEXER_MAX_KEYS,
+                " keys here (block_table columns * block_size, or the key's sequence dimension), but now it is ", cap);
+    TORCH_CHECK(query.stride(qd - 1) == 1 && key.stride(kd - 1) == 1, "lightning_indexer: innermost dimension must be contiguous");
+    auto i32c = [](const std::optional<at::Tensor> &t) { return t.has_value() ? std::optional<at::Tensor>(t->contiguous()) : std::nullopt; };
+    const std::optional<at::Tensor> aq = i32c(actual_seq_lengths_query), ak = i32c(actual_seq_lengths_key);
+    const std::optional<at::Tensor> bt = block_table.has_value() && block_table->stride(1) != 1 ? i32c(block_table) : block_table;
+    const at::Tensor w = weights.stride(qd - 2) == 1 ? weights : weights.contiguous();
+    std::vector<int64_t> shape = q_tnd ? std::vector<int64_t>{rows, n2, count} : std::vector<int64_t>{B, S1, n2, count};
+    at::Tensor out = at::empty(shape, query.options().dtype(at::kInt));
+    const int lqc = q_tnd ? MI_LI_QUERY_TND : MI_LI_QUERY_BSND, lkc = paged ? MI_LI_KEY_PA_BSND : k_tnd ? MI_LI_KEY_TND : MI_LI_KEY_BSND;
+    const size_t wsb = mi_lightning_indexer_workspace(lqc, (int)B, (int)S1, rows, cap);
+    at::Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 16)}, at::dtype(at::kByte).device(query.device()));
+    const int rc = mi_lightning_indexer(
+        query.data_ptr(), key.data_ptr(), w.data_ptr(), out.data_ptr<int>(), aq.has_value() ? aq->data_ptr<int>() : nullptr,
+        ak.has_value() ? ak->data_ptr<int>() : nullptr, bt.has_value() ? bt->data_ptr<int>() : nullptr, lqc, lkc, (int)B, (int)S1, rows, (int)n1,
+        (int)n2, (int)D, cap, (int)block_size, bt.has_value() ? bt->stride(0) : 0, query.stride(0), q_tnd ? 0 : query.stride(1),
+        query.stride(qd - 2), w.stride(0), q_tnd ? 0 : w.stride(1), k_tnd ? 0 : key.stride(0), key.stride(k_tnd ? 0 : 1), (int)count, (int)mode,
+        dtype_code(query), ws.data_ptr(), wsb, cur_stream());
+    TORCH_CHECK(rc == 0, "mi_lightning_indexer failed with code ", rc, " (strides of query / key multiples of 8 elements, of weights of 4)");
+    return out;
+}
+
 // SwiGLU + per-row INT8 quantisation; same arguments / returns as swiglu_quant (activation/swiglu_quant.py:87-127).
 std::tuple<at::Tensor, at::Tensor> swiglu_quant(const at::Tensor &x, const at::Tensor &group_list, int64_t group_list_type,
                                                 bool need_quant, bool do_limit, double limit)
@@ -1246,6 +1343,11 @@ TORCH_LIBRARY_FRAGMENT(npu, m)
     m.def("gqa_prefill_block_score(Tensor q, Tensor k_cache, Tensor cu_seqlens, Tensor seq_lens, Tensor req_to_token, Tensor req_pool_indices, "
           "int max_seqlen, float sm_scale, bool lse, Tensor? query_pos=None) -> Tensor");
     m.def("prefill_topk_from_score(Tensor score, Tensor? per_query_seq_lens, int topk, int block_size, bool fused) -> Tensor");
+    m.def(
+        "lightning_indexer(Tensor query, Tensor key, Tensor weights, Tensor? actual_seq_lengths_query=None, "
+        "Tensor? actual_seq_lengths_key=None, Tensor? block_table=None, "
+        "str? layout_query=None, str? layout_key=None, "
+        "int? sparse_count=None, int? sparse_mode=None) -> Tensor");
     m.def("attn_residual_mix(Tensor prefix_sum, Tensor bank, int num_valid_blocks, Tensor combined_weight, float variance_epsilon) -> Tensor");
     m.def("mul_add(Tensor routed_input, Tensor shared_input, float scaling_factor) -> Tensor");
     m.def("zero_experts_compute_identity(Tensor(a!) expert_indices, Tensor(b!) expert_scales, int num_experts, Tensor hidden_states, "
@@ -1288,6 +1390,7 @@ TORCH_LIBRARY_IMPL(npu, CUDA, m)
     m.impl("topk_append_local_block", TORCH_FN(sglang::npu_kernel::topk_append_local_block));
     m.impl("gqa_prefill_block_score", TORCH_FN(sglang::npu_kernel::gqa_prefill_block_score));
     m.impl("prefill_topk_from_score", TORCH_FN(sglang::npu_kernel::prefill_topk_from_score));
+    m.impl("lightning_indexer", TORCH_FN(sglang::npu_kernel::lightning_indexer));
     m.impl("attn_residual_mix", TORCH_FN(sglang::npu_kernel::attn_residual_mix));
     m.impl("mul_add", TORCH_FN(sglang::npu_kernel::mul_add));
     m.impl("zero_experts_compute_identity", TORCH_FN(sglang::npu_kernel::zero_experts_compute_identity));
