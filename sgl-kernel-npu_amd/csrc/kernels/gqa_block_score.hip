@@ -6,7 +6,8 @@
 // Two stream-ordered launches, both sized from host integers (shapes, max_seqblock) only -- nothing is read back, the op replays in a graph:
 //
 //  score   a workgroup of 4 waves owns (sequence, kv head, block of query heads, run of logical KV blocks); wave w takes the run's blocks
-//          w, w + 4, ...  There is no V, no P.V, no accumulator and no LDS: a wave loads 16 keys x head_dim of its block straight into the
+//          w, w + 4, ... through score_blocks of block_score_dev.h, the engine the prefill form (gqa_block_score_prefill.hip) runs too.
+//          There is no V, no P.V, no accumulator and no LDS: a wave loads 16 keys x head_dim of its block straight into the
 //          A operand of mfma_f32_16x16x32 (lane (g, c16): key c16, dims ks*32 + 8g .. +8 -- every K byte is loaded once, by one lane),
 //          S^T = K.Q^T against the Q^T fragments of all heads of the group it keeps in registers, so every K byte leaves HBM once per kv
 //          head.  Keys are masked by logical position against the row's own length; the per-block maximum (and, for "lse", the exp2 sum,
@@ -31,24 +32,17 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "gqa_common.h"
+#include "block_score_dev.h"
 #include "mi_sgl_kernels.h"
 
 namespace mi_gqa_score {
 using namespace mi_gqa;
 
-constexpr int kMaxSeqBlock = 16384, kIdxBits = 14, kMaxTopk = 1024;
-static_assert((1 << kIdxBits) == kMaxSeqBlock, "a block id fills the key's low bits");
-
 struct Params {
     const uint16_t *q, *k;
     const int32_t *seq_lens;        // [batch] (sl_sb = 1, sl_sh = 0) or, packed, [batch * group] (sl_sb = group, sl_sh = 1)
     int sl_sb, sl_sh;
-    const void *table;              // block_table [batch, columns], or req_to_token [requests, cols] when req_pool is set
-    int table_i64;
-    int64_t tb_sr, tb_sc;
-    const void *req_pool;           // [batch]; null = block-table form
-    int req_i64, rtt_cols, num_pages, sanitize;
+    PageMap pages;
     float *scores;                  // [batch, q_heads, max_seqblock]
     int32_t *out;                   // [q_heads, batch, topk (+ 1 with append_blocks > 0)]
     int batch, q_heads, kv_heads, group, block_size, bs_shift, max_seqblock, max_kv_len, topk, init_blocks, local_blocks, lse, append_blocks, d;
@@ -57,10 +51,6 @@ struct Params {
     float sm_scale;
 };
 
-__device__ __forceinline__ int64_t load_index(const void *base, int is_i64, int64_t off)
-{
-    return is_i64 ? ((const int64_t *)base)[off] : (int64_t)((const int32_t *)base)[off];
-}
 __device__ __forceinline__ int row_len(const Params &p, int b, int hg)
 {
     return min(max(p.seq_lens[(int64_t)b * p.sl_sb + (int64_t)hg * p.sl_sh], 0), p.max_kv_len);
@@ -77,7 +67,7 @@ __device__ __forceinline__ int group_max_len(const Params &p, int b)      // the
 template <bool BF16, int DP, int HB, bool LSE>
 __global__ __launch_bounds__(256) void gqa_block_score_kernel(Params p)
 {
-    constexpr int QS = DP / 32, UP = DP <= 128 ? 4 : 2;           // k-steps of a key row; 16-key units of a load stage
+    constexpr int QS = DP / 32;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, c16 = lane & 15;
     int u = blockIdx.x;                                           // the grid is exactly batch * kv_heads * runs * head_blocks
@@ -86,7 +76,7 @@ __global__ __launch_bounds__(256) void gqa_block_score_kernel(Params p)
     const int run = u % p.runs;
     u /= p.runs;
     const int kvh = u % p.kv_heads, b = u / p.kv_heads;
-    const int BS = p.block_size, shift = p.bs_shift, ushift = shift - 4, units = BS >> 4;
+    const int BS = p.block_size, shift = p.bs_shift;
 
     const int len_max = group_max_len(p, b);
     const int nb_max = (len_max + BS - 1) >> shift;
@@ -94,7 +84,6 @@ __global__ __launch_bounds__(256) void gqa_block_score_kernel(Params p)
     const int jw = run * p.blocks_per_wg + wave;                  // this wave's blocks: jw, jw + 4, ... below j1
     const int j1 = min((run + 1) * p.blocks_per_wg, nb_max);
     if (jw >= j1) return;                                         // no LDS, no barrier: waves are on their own
-    const int T = __builtin_amdgcn_readfirstlane(((j1 - jw + 3) >> 2) << ushift);      // 16-key units of this wave
 
     // Q^T fragments: lane (g, c16) holds q[head][ks*32 + g*8 .. +8] of head block hb; its row's length
     s16x8 qf[HB][QS];
@@ -112,104 +101,13 @@ __global__ __launch_bounds__(256) void gqa_block_score_kernel(Params p)
             qf[hb][ks] = (ok && d < p.d) ? *(const s16x8 *)(qrow + d) : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
         }
     }
-    const float cs = p.sm_scale * 1.4426950408889634f;
-
-    // unit t of the wave: rows 16 (t mod units) .. +16 of block jw + 4 (t / units); lane loads dims ks*32 + 8g .. +8 of row c16.  The pages of
-    // a stage's units are looked up by its first lanes (one vector load for the stage, not a scalar chain per unit) and read lane by lane.
-    auto load_stage = [&](int t0, u32x4(&kr)[UP][QS]) {
-        const int tl = t0 + (lane & (UP - 1)), jl = jw + 4 * (tl >> ushift);
-        int page_l = 0;
-        if (tl < T) {                                             // jl < j1 <= nb_max: inside the table
-            int64_t page;
-            if (p.req_pool) {
-                const int64_t col = min((int64_t)jl * BS, (int64_t)p.rtt_cols - 1);
-                page = load_index(p.table, p.table_i64, load_index(p.req_pool, p.req_i64, b) * p.tb_sr + col * p.tb_sc) / BS;
-                if (p.sanitize) page = min(max(page, (int64_t)0), (int64_t)p.num_pages - 1);
-            } else {
-                page = load_index(p.table, p.table_i64, b * p.tb_sr + jl * p.tb_sc);
-            }
-            page_l = (int)page;
-        }
-#pragma unroll
-        for (int i = 0; i < UP; ++i) {
-            const int t = t0 + i;
-            const int j = jw + 4 * (t >> ushift), n = ((t & (units - 1)) << 4) + c16;
-            const int64_t page = __builtin_amdgcn_readlane(page_l, i);
-            const bool ok = t < T && j * BS + n < len_max;        // rows behind the longest length are zeros and are never read
-            const uint16_t *krow = p.k + page * p.k_sblk + (int64_t)n * p.k_srow + (int64_t)kvh * p.k_sh;
-#pragma unroll
-            for (int ks = 0; ks < QS; ++ks) {
-                const int d = ks * 32 + g * 8;
-                kr[i][ks] = (ok && d < p.d) ? *(const u32x4 *)(krow + d) : u32x4{0, 0, 0, 0};
-            }
-        }
-    };
-
-    // per lane and head block: running maximum and (LSE) exp2 sum over the lane's keys 4g + r of the block's units seen so far
-    float m_run[HB], l_run[HB];
-#pragma unroll
-    for (int hb = 0; hb < HB; ++hb) m_run[hb] = -INFINITY, l_run[hb] = 0.f;
-
-    auto compute_stage = [&](int t0, const u32x4(&kr)[UP][QS]) {
-#pragma unroll
-        for (int i = 0; i < UP; ++i) {
-            const int t = t0 + i;
-            if (t >= T) break;                                    // wave-uniform
-            const int j = jw + 4 * (t >> ushift), un = t & (units - 1);
-            const int pos0 = j * BS + (un << 4) + 4 * g;          // logical position of this lane's key r = 0
-#pragma unroll
-            for (int hb = 0; hb < HB; ++hb) {
-                f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int ks = 0; ks < QS; ++ks) s = mfma16<BF16>(__builtin_bit_cast(s16x8, kr[i][ks]), qf[hb][ks], s);
-                const int lim = len_row[hb] - pos0;               // keys r < lim take part
-                float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = r < lim ? s[r] * cs : -INFINITY;
-                const float um = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-                const float m_new = fmaxf(m_run[hb], um);
-                if constexpr (LSE) {
-                    if (m_new > -INFINITY) {
-                        float e = l_run[hb] * __builtin_amdgcn_exp2f(m_run[hb] - m_new);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) e += __builtin_amdgcn_exp2f(v[r] - m_new);
-                        l_run[hb] = e;
-                    }
-                }
-                m_run[hb] = m_new;
-            }
-            if (un == units - 1) {                                // the block is complete: the four lane rows meet
-#pragma unroll
-                for (int hb = 0; hb < HB; ++hb) {
-                    const float M = max_over_rows(m_run[hb]);
-                    float score = M;
-                    if constexpr (LSE) {
-                        const float part = M > -INFINITY ? l_run[hb] * __builtin_amdgcn_exp2f(m_run[hb] - M) : 0.f;
-                        score = M + __builtin_amdgcn_logf(sum_over_rows(part));
-                        if (score != score) score = -INFINITY;
-                    }
-                    if (g == 0 && head[hb] >= 0) p.scores[((int64_t)b * p.q_heads + head[hb]) * p.max_seqblock + j] = score;
-                    m_run[hb] = -INFINITY, l_run[hb] = 0.f;
-                }
-            }
-        }
-    };
-
-    u32x4 ka[UP][QS], kb[UP][QS];
-    load_stage(0, ka);
-    for (int t0 = 0; t0 < T; t0 += 2 * UP) {
-        load_stage(t0 + UP, kb);                                  // travels under the MFMAs of the stage before it
-        compute_stage(t0, ka);
-        load_stage(t0 + 2 * UP, ka);
-        compute_stage(t0 + UP, kb);
-    }
-}
-
-__device__ __forceinline__ uint64_t block_key(float score, int j)      // smaller = better: higher score first, then the lower block id
-{
-    const uint32_t u = __float_as_uint(score);
-    const uint32_t asc = (u >> 31) ? ~u : (u | 0x80000000u);
-    return ((uint64_t)(~asc) << kIdxBits) | (uint32_t)j;
+    // every block takes the per-row mask (lim_min 0); rows at or behind the group's longest length are zeros and are never read
+    score_blocks<BF16, DP, HB, LSE>(
+        KeyRows{p.k + (int64_t)kvh * p.k_sh, p.k_sblk, p.k_srow, p.d, BS, shift}, jw, j1, qf, len_row, len_max, 0, p.sm_scale * 1.4426950408889634f,
+        [&](int j) { return page_of(p.pages, b, j, BS); },
+        [&](int hb, int j, float score) {
+            if (head[hb] >= 0) p.scores[((int64_t)b * p.q_heads + head[hb]) * p.max_seqblock + j] = score;
+        });
 }
 
 // one workgroup per (sequence, query head); P = power of two >= max(2, topk); LDS: P keys (8 B), max_seqblock scores (4 B), 16 words
@@ -269,15 +167,7 @@ __global__ __launch_bounds__(256) void gqa_block_select_kernel(Params p, int P, 
     }
     for (int t = k + tid; t < P; t += 256) cand[t] = ~0ull;
     __syncthreads();
-    for (int size = 2; size <= P; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < (P >> 1); i += 256) {
-                const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-                const uint64_t a = cand[lo], c = cand[hi];
-                if ((a > c) == ((lo & size) == 0)) cand[lo] = c, cand[hi] = a;
-            }
-            __syncthreads();
-        }
+    bitonic_sort<256>(cand, P);
     for (int t = tid; t < p.topk; t += 256) {
         const int v = t < k ? checked((int)(cand[t] & (kMaxSeqBlock - 1))) : -1;
         orow[t] = v;
@@ -309,29 +199,6 @@ __global__ __launch_bounds__(256) void topk_append_local_kernel(const int32_t *i
     if (lane == 0) out[row * (topk + 1) + topk] = any ? -1 : local;
 }
 
-static int padded_dim(int d) { return d <= 64 ? 64 : d <= 128 ? 128 : d <= 256 ? 256 : 0; }
-
-template <bool BF16, int DP, int HB>
-static void launch_lse(const Params &p, unsigned grid, hipStream_t st)
-{
-    if (p.lse) gqa_block_score_kernel<BF16, DP, HB, true><<<grid, 256, 0, st>>>(p);
-    else gqa_block_score_kernel<BF16, DP, HB, false><<<grid, 256, 0, st>>>(p);
-}
-template <bool BF16, int HB>
-static void launch_dim(int dp, const Params &p, unsigned grid, hipStream_t st)
-{
-    if (dp == 64) launch_lse<BF16, 64, HB>(p, grid, st);
-    else if (dp == 128) launch_lse<BF16, 128, HB>(p, grid, st);
-    else launch_lse<BF16, 256, HB>(p, grid, st);
-}
-
-static int cus()
-{
-    int d = 0, n = 0;
-    if (hipGetDevice(&d) != hipSuccess) return 256;
-    return (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0) ? n : 256;
-}
-
 }  // namespace mi_gqa_score
 
 using namespace mi_gqa_score;
@@ -352,33 +219,23 @@ extern "C" int mi_gqa_block_score_topk(const void *q, const void *k, int32_t *to
                                        int dtype, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (batch < 0 || q_heads <= 0 || kv_heads <= 0 || q_heads % kv_heads) return MI_SGL_EINVAL;
-    if (block_size != 16 && block_size != 32 && block_size != 64 && block_size != 128) return MI_SGL_EINVAL;
-    const int dp = padded_dim(head_dim);
-    if (head_dim <= 0 || (head_dim % 8) || !dp) return MI_SGL_EINVAL;
-    if (dtype != MI_DTYPE_BF16 && dtype != MI_DTYPE_F16) return MI_SGL_EINVAL;
-    if (!(sm_scale > 0.f)) return MI_SGL_EINVAL;
-    if (max_seqblock <= 0 || max_seqblock > kMaxSeqBlock || topk <= 0 || topk > kMaxTopk) return MI_SGL_EINVAL;      // the declared limits
+    if (!block_args_ok(block_size, head_dim, dtype, sm_scale)) return MI_SGL_EINVAL;
+    if (!within_limits(max_seqblock, topk)) return MI_SGL_EINVAL; // the declared limits
     if (init_blocks < 0 || local_blocks < 0 || append_local_num_blocks < 0) return MI_SGL_EINVAL;
     const bool direct = req_to_token != nullptr;
     if (direct == (block_table != nullptr) || direct != (req_pool_indices != nullptr)) return MI_SGL_EINVAL;
     if (direct ? (rtt_cols <= 0 || num_pages <= 0) : bt_cols <= 0) return MI_SGL_EINVAL;
     if (batch == 0) return MI_SGL_OK;
     if (!q || !k || !topk_idx || !seq_lens) return MI_SGL_EINVAL;
-    if ((q_stride_h % 8) || (q_stride_b % 8) || (k_stride_row % 8) || (k_stride_blk % 8) || (k_stride_h % 8)) return MI_SGL_EINVAL;   // 16-byte loads
+    if (!aligned8({q_stride_h, q_stride_b, k_stride_row, k_stride_blk, k_stride_h})) return MI_SGL_EINVAL;
     if (!workspace || ((uintptr_t)workspace & 3) || workspace_bytes < mi_gqa_block_score_topk_workspace(batch, q_heads, max_seqblock))
         return MI_SGL_EINVAL;
     Params p;
     p.q = (const uint16_t *)q, p.k = (const uint16_t *)k, p.seq_lens = seq_lens;
     p.group = q_heads / kv_heads;
     p.sl_sb = packed_seq_lens ? p.group : 1, p.sl_sh = packed_seq_lens ? 1 : 0;
-    if (direct) {
-        p.table = req_to_token, p.table_i64 = req_to_token_is_i64, p.tb_sr = rtt_stride_r, p.tb_sc = rtt_stride_t;
-        p.req_pool = req_pool_indices, p.req_i64 = req_pool_is_i64;
-    } else {
-        p.table = block_table, p.table_i64 = block_table_is_i64, p.tb_sr = bt_stride_b, p.tb_sc = bt_stride_n;
-        p.req_pool = nullptr, p.req_i64 = 0;
-    }
-    p.rtt_cols = rtt_cols, p.num_pages = num_pages, p.sanitize = sanitize_page_ids;
+    p.pages = make_page_map(block_table, block_table_is_i64, bt_stride_b, bt_stride_n, req_to_token, req_to_token_is_i64, rtt_stride_r,
+                            rtt_stride_t, rtt_cols, req_pool_indices, req_pool_is_i64, num_pages, sanitize_page_ids);
     p.scores = (float *)workspace, p.out = topk_idx;
     p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.block_size = block_size, p.bs_shift = __builtin_ctz(block_size);
     p.max_seqblock = max_seqblock;
@@ -400,10 +257,11 @@ extern "C" int mi_gqa_block_score_topk(const void *q, const void *k, int32_t *to
     const long long wgs = cells * p.runs;
     if (wgs > 0x7fffffffll || (long long)batch * q_heads > 0x7fffffffll) return MI_SGL_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (max_seqblock > topk) {                                    // otherwise no sequence can hold more than topk blocks: select alone
-        if (dtype == MI_DTYPE_BF16) hb == 1 ? launch_dim<true, 1>(dp, p, (unsigned)wgs, st) : launch_dim<true, 4>(dp, p, (unsigned)wgs, st);
-        else hb == 1 ? launch_dim<false, 1>(dp, p, (unsigned)wgs, st) : launch_dim<false, 4>(dp, p, (unsigned)wgs, st);
-    }
+    if (max_seqblock > topk)                                      // otherwise no sequence can hold more than topk blocks: select alone
+        dispatch(dtype == MI_DTYPE_BF16, padded_dim(head_dim), p.lse, [&](auto bf, auto dp, auto lse) {
+            if (hb == 1) gqa_block_score_kernel<bf(), dp(), 1, lse()><<<(unsigned)wgs, 256, 0, st>>>(p);
+            else gqa_block_score_kernel<bf(), dp(), 4, lse()><<<(unsigned)wgs, 256, 0, st>>>(p);
+        });
     int P = 2;
     while (P < topk) P *= 2;
     const int sc_words = (max_seqblock + 3) / 4 * 4;

@@ -9,23 +9,23 @@
 //  score   a workgroup of 4 waves owns (a tile of TQ consecutive tokens of ONE request, a kv head, a run of logical KV blocks).  TQ x group
 //          rows (token-major, TQ = 64 / group) are flattened into four 16-row MFMA column blocks whose Q^T fragments every wave keeps in
 //          registers; wave w takes the run's blocks w, w + 4, ...  A 16-key unit of K is loaded straight into the A operand of
-//          mfma_f32_16x16x32 (the scheme of gqa_block_score_kernel: no V, no P.V, no accumulator, no LDS, no barrier) and multiplied into all
-//          four column blocks; the per-lane online maximum / exp2 sum is fp32 in the log2 domain and the four lane rows meet in permlane swaps
-//          when a block ends.  The grid is the host bound ceil(total_q / TQ) + requests tiles (the tokens behind the last request count as
-//          one more request); a workgroup finds its request and tile by walking cu_seqlens.  Pages come straight from req_to_token: neither
-//          the reference's per-q-block mapping tensors nor its [q blocks, max_blocks] table exist.
+//          mfma_f32_16x16x32 (score_blocks of block_score_dev.h, the engine gqa_block_score_kernel runs too: no V, no P.V, no accumulator,
+//          no LDS, no barrier) and multiplied into all four column blocks; the per-lane online maximum / exp2 sum is fp32 in the log2 domain
+//          and the four lane rows meet in permlane swaps when a block ends.  The grid is the host bound ceil(total_q / TQ) + requests tiles
+//          (the tokens behind the last request count as one more request); a workgroup finds its request and tile by walking cu_seqlens.
+//          Pages come straight from req_to_token: neither the reference's per-q-block mapping tensors nor its [q blocks, max_blocks] table
+//          exist.
 //          Causality is exploited, not only masked.  With lim(t) = min(L, pos(t) + 1) the keys visible to token t: blocks at or behind
 //          ceil(max_t lim / bs) are neither looked up nor loaded (the tile writes their -inf), K rows at or behind max_t lim are zeros that
 //          are never read, blocks that end at or below min_t lim take no per-row mask, and only the blocks between compare per row.
 //          Workgroup order: tile fastest, then run, then kv head -- the workgroups resident at one time are the tiles of one request against
 //          the SAME run of keys (2048 keys: 512 KB at head dim 128), which they share through L2.
 //  select  one wave per (head, token) row, four rows per workgroup, no workgroup barrier.  Every block has the distinct 46-bit key
-//          (descending-order image of its score) << 14 | j of gqa_block_score.hip; k = min(topk, scores above -inf); the k-th smallest key is
-//          found by bisection on the key's bits (ballots; the keys of rows of up to 512 blocks stay in registers, longer rows are re-read),
-//          the k winners are compacted into the wave's own LDS slice and each finds its rank by counting.  Fused form: entries that start
-//          behind the token's position become -1 in place and slot topk receives the causal-local block.
+//          (descending-order image of its score) << 14 | j (block_key, shared with the decode form); k = min(topk, scores above -inf); the
+//          k-th smallest key is found by bisection on the key's bits (ballots; the keys of rows of up to 512 blocks stay in registers, longer
+//          rows are re-read), the k winners are compacted into the wave's own LDS slice and each finds its rank by counting.  Fused form:
+//          entries that start behind the token's position become -1 in place and slot topk receives the causal-local block.
 //
-// gqa_block_score.hip and gqa_common.h are untouched: block_key is restated here (14 index bits, the same order).
 // LIMITS (refused with MI_SGL_EINVAL, never a silent wrong answer): max_seqblock <= 16384; topk <= 1024; block_size 16 / 32 / 64 / 128;
 // head_dim a multiple of 8 up to 256 (padded with zeros to 64 / 128 / 256); sm_scale > 0.
 #include <algorithm>
@@ -34,40 +34,33 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "gqa_common.h"
+#include "block_score_dev.h"
 #include "mi_sgl_kernels.h"
 
 namespace mi_gqa_prefill_score {
 using namespace mi_gqa;
 
-constexpr int kMaxSeqBlock = 16384, kIdxBits = 14, kMaxTopk = 1024;
 constexpr int kColBlocks = 4, kTileRows = 16 * kColBlocks;       // rows (token, head) of a workgroup
 constexpr int kRunKeys = 2048;                                   // keys of a run of blocks
 constexpr int kSelRegIters = 8;                                  // select: rows of up to 64 * 8 blocks keep their keys in registers
-static_assert((1 << kIdxBits) == kMaxSeqBlock, "a block id fills the key's low bits");
 
 struct Params {
     const uint16_t *q, *k;
     float *score;                   // [heads, total_q, max_seqblock]
-    const void *cu, *seq_lens, *table, *req_pool, *qpos;
-    int cu_i64, sl_i64, table_i64, req_i64, qpos_i64;
-    int64_t tb_sr, tb_sc;
-    int rtt_cols, total_q, nreq, heads, kv_heads, group, gc, tq, head_blocks, block_size, bs_shift, max_seqblock, d;
+    const void *cu, *seq_lens, *qpos;
+    int cu_i64, sl_i64, qpos_i64;
+    PageMap pages;                  // always the req_to_token form
+    int total_q, nreq, heads, kv_heads, group, gc, tq, head_blocks, block_size, bs_shift, max_seqblock, d;
     int tiles, runs, blocks_per_wg;
     int64_t q_st, q_sh, k_sblk, k_srow, k_sh, s_sh, s_st;
     float sm_scale;
 };
 
-__device__ __forceinline__ int64_t load_index(const void *base, int is_i64, int64_t off)
-{
-    return is_i64 ? ((const int64_t *)base)[off] : (int64_t)((const int32_t *)base)[off];
-}
-
 // DP: compile-time padded head dim (64, 128, 256)
 template <bool BF16, int DP, bool LSE>
 __global__ __launch_bounds__(256) void gqa_prefill_block_score_kernel(Params p)
 {
-    constexpr int CB = kColBlocks, QS = DP / 32, UP = DP <= 128 ? 4 : 2;      // k-steps of a key row; 16-key units of a load stage
+    constexpr int CB = kColBlocks, QS = DP / 32;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, c16 = lane & 15;
     int u = blockIdx.x;                                           // the grid is exactly tiles * runs * kv_heads * head_blocks
@@ -76,7 +69,7 @@ __global__ __launch_bounds__(256) void gqa_prefill_block_score_kernel(Params p)
     const int run = u % p.runs;
     u /= p.runs;
     const int hblk = u % p.head_blocks, kvh = u / p.head_blocks;
-    const int BS = p.block_size, shift = p.bs_shift, ushift = shift - 4, units = BS >> 4;
+    const int BS = p.block_size, shift = p.bs_shift;
 
     // the tile's request: tiles are dealt request by request, ceil(q_len / TQ) each; what is left covers the tokens behind cu[nreq]
     int req = -1;
@@ -107,7 +100,7 @@ __global__ __launch_bounds__(256) void gqa_prefill_block_score_kernel(Params p)
         const int64_t sl = load_index(p.seq_lens, p.sl_i64, req);
         L = (int)min(max(sl, (int64_t)0), (int64_t)p.max_seqblock * BS);
         pos_base = sl - q_len;
-        pool_row = load_index(p.req_pool, p.req_i64, req);
+        pool_row = load_index(p.pages.req_pool, p.pages.req_i64, req);
     }
     auto lim_of = [&](int64_t t) -> int {
         if (req < 0) return 0;
@@ -128,8 +121,6 @@ __global__ __launch_bounds__(256) void gqa_prefill_block_score_kernel(Params p)
     const int j1 = min(jrun1, nb_tile);
 
     if (jw < j1) {                                                // no LDS, no barrier: waves are on their own
-        const int T = __builtin_amdgcn_readfirstlane(((j1 - jw + 3) >> 2) << ushift);      // 16-key units of this wave
-
         // Q^T fragments: lane (g, c16) holds q[token][head][ks*32 + g*8 .. +8] of row cb * 16 + c16 = (token, head) token-major; its lim
         s16x8 qf[CB][QS];
         int lim_row[CB];
@@ -149,96 +140,13 @@ __global__ __launch_bounds__(256) void gqa_prefill_block_score_kernel(Params p)
                 qf[cb][ks] = (ok && d < p.d) ? *(const s16x8 *)(qrow + d) : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
             }
         }
-        const float cs = p.sm_scale * 1.4426950408889634f;
-
-        // unit t of the wave: rows 16 (t mod units) .. +16 of block jw + 4 (t / units); lane loads dims ks*32 + 8g .. +8 of row c16.  The pages
-        // of a stage's units are looked up by its first lanes (one vector load for the stage) and read lane by lane.
-        auto load_stage = [&](int t0u, u32x4(&kr)[UP][QS]) {
-            const int tl = t0u + (lane & (UP - 1)), jl = jw + 4 * (tl >> ushift);
-            int page_l = 0;
-            if (tl < T) {                                         // jl < j1 <= nb_tile <= ceil(L / BS)
-                const int64_t col = min((int64_t)jl * BS, (int64_t)p.rtt_cols - 1);
-                page_l = (int)(load_index(p.table, p.table_i64, pool_row * p.tb_sr + col * p.tb_sc) / BS);
-            }
-#pragma unroll
-            for (int i = 0; i < UP; ++i) {
-                const int t = t0u + i;
-                const int j = jw + 4 * (t >> ushift), n = ((t & (units - 1)) << 4) + c16;
-                const int64_t page = __builtin_amdgcn_readlane(page_l, i);
-                const bool ok = t < T && j * BS + n < lim_max;    // rows no row of the tile sees are zeros and are never read
-                const uint16_t *krow = p.k + page * p.k_sblk + (int64_t)n * p.k_srow + (int64_t)kvh * p.k_sh;
-#pragma unroll
-                for (int ks = 0; ks < QS; ++ks) {
-                    const int d = ks * 32 + g * 8;
-                    kr[i][ks] = (ok && d < p.d) ? *(const u32x4 *)(krow + d) : u32x4{0, 0, 0, 0};
-                }
-            }
-        };
-
-        // per lane and column block: running maximum and (LSE) exp2 sum over the lane's keys 4g + r of the block's units seen so far
-        float m_run[CB], l_run[CB];
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) m_run[cb] = -INFINITY, l_run[cb] = 0.f;
-
-        auto compute_stage = [&](int t0u, const u32x4(&kr)[UP][QS]) {
-#pragma unroll
-            for (int i = 0; i < UP; ++i) {
-                const int t = t0u + i;
-                if (t >= T) break;                                // wave-uniform
-                const int j = jw + 4 * (t >> ushift), un = t & (units - 1);
-                const int pos0 = j * BS + (un << 4) + 4 * g;      // logical position of this lane's key r = 0
-                const bool front = (j + 1) * BS <= lim_min;       // wave-uniform: every row of the tile sees the whole block
-#pragma unroll
-                for (int cb = 0; cb < CB; ++cb) {
-                    f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int ks = 0; ks < QS; ++ks) s = mfma16<BF16>(__builtin_bit_cast(s16x8, kr[i][ks]), qf[cb][ks], s);
-                    float v[4];
-                    if (front) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = s[r] * cs;
-                    } else {
-                        const int lim = lim_row[cb] - pos0;       // keys r < lim take part
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = r < lim ? s[r] * cs : -INFINITY;
-                    }
-                    const float um = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-                    const float m_new = fmaxf(m_run[cb], um);
-                    if constexpr (LSE) {
-                        if (m_new > -INFINITY) {
-                            float e = l_run[cb] * __builtin_amdgcn_exp2f(m_run[cb] - m_new);
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) e += __builtin_amdgcn_exp2f(v[r] - m_new);
-                            l_run[cb] = e;
-                        }
-                    }
-                    m_run[cb] = m_new;
-                }
-                if (un == units - 1) {                            // the block is complete: the four lane rows meet
-#pragma unroll
-                    for (int cb = 0; cb < CB; ++cb) {
-                        const float M = max_over_rows(m_run[cb]);
-                        float score = M;
-                        if constexpr (LSE) {
-                            const float part = M > -INFINITY ? l_run[cb] * __builtin_amdgcn_exp2f(m_run[cb] - M) : 0.f;
-                            score = M + __builtin_amdgcn_logf(sum_over_rows(part));
-                            if (score != score) score = -INFINITY;
-                        }
-                        if (g == 0 && srow[cb] >= 0) p.score[srow[cb] + j] = score;
-                        m_run[cb] = -INFINITY, l_run[cb] = 0.f;
-                    }
-                }
-            }
-        };
-
-        u32x4 ka[UP][QS], kb[UP][QS];
-        load_stage(0, ka);
-        for (int t0u = 0; t0u < T; t0u += 2 * UP) {
-            load_stage(t0u + UP, kb);                             // travels under the MFMAs of the stage before it
-            compute_stage(t0u, ka);
-            load_stage(t0u + 2 * UP, ka);
-            compute_stage(t0u + UP, kb);
-        }
+        // jl < j1 <= nb_tile <= ceil(L / BS); rows no row of the tile sees are zeros and are never read; blocks every row sees whole skip the mask
+        score_blocks<BF16, DP, CB, LSE>(
+            KeyRows{p.k + (int64_t)kvh * p.k_sh, p.k_sblk, p.k_srow, p.d, BS, shift}, jw, j1, qf, lim_row, lim_max, lim_min,
+            p.sm_scale * 1.4426950408889634f, [&](int j) { return page_of_row(p.pages, pool_row, j, BS); },
+            [&](int cb, int j, float score) {
+                if (srow[cb] >= 0) p.score[srow[cb] + j] = score;
+            });
     }
 
     // the run's blocks at or behind nb_tile: -inf for every row of the tile (wave w: rows w, w + 4, ...; lanes along the blocks)
@@ -252,13 +160,6 @@ __global__ __launch_bounds__(256) void gqa_prefill_block_score_kernel(Params p)
             for (int j = jf0 + lane; j < jrun1; j += 64) dst[j] = -INFINITY;
         }
     }
-}
-
-__device__ __forceinline__ uint64_t block_key(float score, int j)      // smaller = better: higher score first, then the lower block id
-{
-    const uint32_t u = __float_as_uint(score);
-    const uint32_t asc = (u >> 31) ? ~u : (u | 0x80000000u);
-    return ((uint64_t)(~asc) << kIdxBits) | (uint32_t)j;
 }
 
 struct SelParams {
@@ -348,22 +249,6 @@ __global__ __launch_bounds__(256) void prefill_block_select_kernel(SelParams p)
     if (p.fused && lane == 0) orow[p.topk] = any ? -1 : local;
 }
 
-static int padded_dim(int d) { return d <= 64 ? 64 : d <= 128 ? 128 : d <= 256 ? 256 : 0; }
-
-template <bool BF16, int DP>
-static void launch_lse(bool lse, const Params &p, unsigned grid, hipStream_t st)
-{
-    if (lse) gqa_prefill_block_score_kernel<BF16, DP, true><<<grid, 256, 0, st>>>(p);
-    else gqa_prefill_block_score_kernel<BF16, DP, false><<<grid, 256, 0, st>>>(p);
-}
-template <bool BF16>
-static void launch_dim(int dp, bool lse, const Params &p, unsigned grid, hipStream_t st)
-{
-    if (dp == 64) launch_lse<BF16, 64>(lse, p, grid, st);
-    else if (dp == 128) launch_lse<BF16, 128>(lse, p, grid, st);
-    else launch_lse<BF16, 256>(lse, p, grid, st);
-}
-
 }  // namespace mi_gqa_prefill_score
 
 using namespace mi_gqa_prefill_score;
@@ -377,22 +262,18 @@ extern "C" int mi_gqa_prefill_block_score(const void *q, const void *k, float *s
                                           int64_t s_stride_h, int64_t s_stride_t, float sm_scale, int dtype, void *stream)
 {
     if (total_q < 0 || num_reqs < 0 || idx_heads <= 0 || kv_heads <= 0 || idx_heads % kv_heads) return MI_SGL_EINVAL;
-    if (block_size != 16 && block_size != 32 && block_size != 64 && block_size != 128) return MI_SGL_EINVAL;
-    const int dp = padded_dim(head_dim);
-    if (head_dim <= 0 || (head_dim % 8) || !dp) return MI_SGL_EINVAL;
-    if (dtype != MI_DTYPE_BF16 && dtype != MI_DTYPE_F16) return MI_SGL_EINVAL;
-    if (!(sm_scale > 0.f)) return MI_SGL_EINVAL;
+    if (!block_args_ok(block_size, head_dim, dtype, sm_scale)) return MI_SGL_EINVAL;
     if (max_seqblock <= 0 || max_seqblock > kMaxSeqBlock || rtt_cols <= 0) return MI_SGL_EINVAL;      // the declared limits
     if (total_q == 0) return MI_SGL_OK;
     if (!q || !k || !score || !cu_seqlens) return MI_SGL_EINVAL;
     if (num_reqs > 0 && (!seq_lens || !req_to_token || !req_pool_indices)) return MI_SGL_EINVAL;
-    if ((q_stride_h % 8) || (q_stride_t % 8) || (k_stride_row % 8) || (k_stride_blk % 8) || (k_stride_h % 8)) return MI_SGL_EINVAL;   // 16-byte loads
+    if (!aligned8({q_stride_h, q_stride_t, k_stride_row, k_stride_blk, k_stride_h})) return MI_SGL_EINVAL;
     Params p;
     p.q = (const uint16_t *)q, p.k = (const uint16_t *)k, p.score = score;
-    p.cu = cu_seqlens, p.seq_lens = seq_lens, p.table = req_to_token, p.req_pool = req_pool_indices, p.qpos = query_pos;
-    p.cu_i64 = cu_seqlens_is_i64, p.sl_i64 = seq_lens_is_i64, p.table_i64 = req_to_token_is_i64, p.req_i64 = req_pool_is_i64;
-    p.qpos_i64 = query_pos_is_i64;
-    p.tb_sr = rtt_stride_r, p.tb_sc = rtt_stride_t, p.rtt_cols = rtt_cols;
+    p.cu = cu_seqlens, p.seq_lens = seq_lens, p.qpos = query_pos;
+    p.cu_i64 = cu_seqlens_is_i64, p.sl_i64 = seq_lens_is_i64, p.qpos_i64 = query_pos_is_i64;
+    p.pages = make_page_map(nullptr, 0, 0, 0, req_to_token, req_to_token_is_i64, rtt_stride_r, rtt_stride_t, rtt_cols, req_pool_indices,
+                            req_pool_is_i64, 0, 0);
     p.total_q = total_q, p.nreq = num_reqs, p.heads = idx_heads, p.kv_heads = kv_heads, p.group = idx_heads / kv_heads;
     // the tile: TQ tokens x gc heads <= 64 rows, token-major; groups above 64 heads take one token and several head blocks
     p.gc = std::min(p.group, kTileRows);
@@ -408,8 +289,9 @@ extern "C" int mi_gqa_prefill_block_score(const void *q, const void *k, float *s
     const long long wgs = (long long)p.tiles * p.runs * kv_heads * p.head_blocks;
     if (wgs > 0x7fffffffll) return MI_SGL_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MI_DTYPE_BF16) launch_dim<true>(dp, score_lse != 0, p, (unsigned)wgs, st);
-    else launch_dim<false>(dp, score_lse != 0, p, (unsigned)wgs, st);
+    dispatch(dtype == MI_DTYPE_BF16, padded_dim(head_dim), score_lse != 0, [&](auto bf, auto dp, auto lse) {
+        gqa_prefill_block_score_kernel<bf(), dp(), lse()><<<(unsigned)wgs, 256, 0, st>>>(p);
+    });
     return hipGetLastError() == hipSuccess ? MI_SGL_OK : MI_SGL_ELAUNCH;
 }
 
@@ -418,7 +300,7 @@ extern "C" int mi_prefill_topk_from_score(const float *score, int64_t s_stride_h
                                           int total_q, int max_seqblock, int topk, int block_size, int fused, void *stream)
 {
     if (heads < 0 || total_q < 0 || block_size <= 0) return MI_SGL_EINVAL;
-    if (max_seqblock <= 0 || max_seqblock > kMaxSeqBlock || topk <= 0 || topk > kMaxTopk) return MI_SGL_EINVAL;      // the declared limits
+    if (!within_limits(max_seqblock, topk)) return MI_SGL_EINVAL; // the declared limits
     if (fused && !per_query_seq_lens) return MI_SGL_EINVAL;
     const int64_t rows = (int64_t)heads * total_q;
     if (rows == 0) return MI_SGL_OK;

@@ -1,14 +1,58 @@
-// Shared by the paged GQA decode kernels (gqa_decode.hip, gqa_sparse_decode.hip): wave reductions, MFMA / packing helpers, the padded LDS row
-// stride, the kernel parameter block and the kernel that merges flash-decoding partials.
+// Shared by the paged GQA decode kernels (gqa_decode.hip, gqa_decode_wide.hip, gqa_sparse_decode.hip) and the indexers (gqa_block_score.hip,
+// gqa_block_score_prefill.hip, lightning_indexer.hip; block_score_dev.h builds on it): the host helpers of the entry points, wave reductions,
+// MFMA / packing helpers, the padded LDS row stride, the kernel parameter block and the kernel that merges flash-decoding partials.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include <initializer_list>
+#include <type_traits>
+
 #include "decode_plan.h"
 #include "mi_sgl_kernels.h"
 
 namespace mi_gqa {
+
+// ---- host helpers of the C entry points
+inline int padded_dim(int d) { return d <= 64 ? 64 : d <= 128 ? 128 : d <= 256 ? 256 : 0; }
+inline int cus()                                                  // CUs of the current device (256 when it cannot be asked), asked once
+{
+    static int cached[64];
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 256;
+    if (!cached[d]) {
+        int n = 0;
+        cached[d] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0) ? n : 256;
+    }
+    return cached[d];
+}
+// what every block-sparse entry point asks of its shapes: block size 16 / 32 / 64 / 128, head dim a multiple of 8 up to 256, bf16 / fp16,
+// sm_scale > 0 (the scaling is applied before the maximum)
+inline bool block_args_ok(int block_size, int head_dim, int dtype, float sm_scale)
+{
+    if (block_size != 16 && block_size != 32 && block_size != 64 && block_size != 128) return false;
+    if (head_dim <= 0 || (head_dim % 8) || !padded_dim(head_dim)) return false;
+    return (dtype == MI_DTYPE_BF16 || dtype == MI_DTYPE_F16) && sm_scale > 0.f;
+}
+inline bool aligned8(std::initializer_list<int64_t> strides)      // 16-byte loads of 2-byte elements
+{
+    for (const int64_t s : strides)
+        if (s % 8) return false;
+    return true;
+}
+// dtype, padded head dim and one more flag as compile-time constants: f(std::true_type{}, std::integral_constant<int, 128>{}, std::false_type{})
+template <class F>
+inline void dispatch(bool bf16, int dp, bool flag, F f)
+{
+    auto dims = [&](auto bf, auto fl) {
+        if (dp == 64) f(bf, std::integral_constant<int, 64>{}, fl);
+        else if (dp == 128) f(bf, std::integral_constant<int, 128>{}, fl);
+        else f(bf, std::integral_constant<int, 256>{}, fl);
+    };
+    auto flags = [&](auto bf) { flag ? dims(bf, std::true_type{}) : dims(bf, std::false_type{}); };
+    bf16 ? flags(std::true_type{}) : flags(std::false_type{});
+}
 
 // Reductions across the four 16-lane rows of a wave through v_permlane16_swap / v_permlane32_swap (VALU) instead of ds_bpermute (an LDS
 // round trip each).  swap16(x): {rows 0,0,2,2 | rows 1,1,3,3} of x; swap32(x): {lower half twice | upper half twice}.  Sums and maxima of

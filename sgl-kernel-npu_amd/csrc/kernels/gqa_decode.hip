@@ -335,21 +335,10 @@ using namespace mi_gqa;
 
 // ---- the planned form (decode_plan.h): a device-built, length-aware work list instead of one split count for every sequence.  Served for
 // plain decode (no sinks, no sliding window, no per-row block tables); MI_GQA_PLAN=0 keeps uniform splits.
-static int gqa_cus()
-{
-    static int cached[64];
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 256;
-    if (!cached[d]) {
-        int n = 0;
-        cached[d] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0) ? n : 256;
-    }
-    return cached[d];
-}
 constexpr int kGqaMaxWgPerCu = 4;
 // rows of partials a planned workspace holds: (items) x (heads of a group) <= batch * q_heads + (workers + padding) * q_heads
-static size_t gqa_plan_rows_cap(int batch, int q_heads) { return (size_t)batch * q_heads + (size_t)(gqa_cus() * kGqaMaxWgPerCu + 8) * q_heads; }
-static size_t gqa_plan_words_cap(int batch, int q_heads) { return mi_sgl::plan_words((long long)batch * q_heads, gqa_cus() * kGqaMaxWgPerCu); }
+static size_t gqa_plan_rows_cap(int batch, int q_heads) { return (size_t)batch * q_heads + (size_t)(cus() * kGqaMaxWgPerCu + 8) * q_heads; }
+static size_t gqa_plan_words_cap(int batch, int q_heads) { return mi_sgl::plan_words((long long)batch * q_heads, cus() * kGqaMaxWgPerCu); }
 static bool gqa_plan_allowed()
 {
     static const bool allow = !(getenv("MI_GQA_PLAN") && atoi(getenv("MI_GQA_PLAN")) == 0);
@@ -444,7 +433,7 @@ static int gqa_decode_impl(const void *q, const void *k, const void *v, void *ou
         if (!planned) {
             const long long wgs = (long long)batch * kv_heads * head_blocks;
             const int ntiles = (max_seq_len + mi_gqa_wide::kTile - 1) / mi_gqa_wide::kTile, cap = ntiles / 8 > 1 ? ntiles / 8 : 1;   // >= 256 keys per split
-            const int fill = (int)std::min<long long>(std::min<long long>((gqa_cus() + wgs - 1) / wgs, cap), 64);
+            const int fill = (int)std::min<long long>(std::min<long long>((cus() + wgs - 1) / wgs, cap), 64);
             num_splits = std::max(1, std::min(num_splits, fill));
         }
         w.num_splits = num_splits;
@@ -452,7 +441,7 @@ static int gqa_decode_impl(const void *q, const void *k, const void *v, void *ou
         w.ws_ml = w.ws_o ? w.ws_o + (planned ? gqa_plan_rows_cap(batch, q_heads) : (size_t)batch * q_heads * num_splits) * mi_gqa_wide::kDVP : nullptr;
         long long units = (long long)batch * kv_heads * num_splits;
         if (planned) {
-            const int workers = std::max(1, gqa_cus() / head_blocks);
+            const int workers = std::max(1, cus() / head_blocks);
             int32_t *plan = (int32_t *)(w.ws_ml + gqa_plan_rows_cap(batch, q_heads) * 2);
             mi_sgl::decode_plan_kernel<<<1, 1024, 0, st>>>(kv_seq_lens, batch, kv_heads, mi_gqa_wide::tile_keys(w), 1, workers, plan);
             w.plan = plan;
@@ -511,7 +500,7 @@ static int gqa_decode_impl(const void *q, const void *k, const void *v, void *ou
         // workgroups the chip runs at once: as many per CU as the LDS of this shape allows; a (sequence, kv head) piece is head_blocks of them
         const size_t lds = 2 * (size_t)shape->tile * ((size_t)shape->dkp * 2 + 32 + (size_t)shape->dvp * 2 + 32);
         const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(kGqaMaxWgPerCu, (160 * 1024) / lds));
-        const int workers = std::max(1, gqa_cus() * per_cu / head_blocks);
+        const int workers = std::max(1, cus() * per_cu / head_blocks);
         int32_t *plan = (int32_t *)(p.ws_ml + gqa_plan_rows_cap(batch, q_heads) * 2);
         mi_sgl::decode_plan_kernel<<<1, 1024, 0, st>>>(kv_seq_lens, batch, kv_heads, shape->tile, 1, workers, plan);
         p.plan = plan;

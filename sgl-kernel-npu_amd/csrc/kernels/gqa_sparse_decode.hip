@@ -22,7 +22,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "gqa_common.h"
+#include "block_score_dev.h"
 #include "mi_sgl_kernels.h"
 
 namespace mi_gqa_sparse {
@@ -38,11 +38,7 @@ struct Params {
     const void *topk;               // [kv_heads, batch, topk] through the three strides
     int topk_i64;
     int64_t ti_sh, ti_sb, ti_st;
-    const void *table;              // block_table [batch, max_blocks], or req_to_token [requests, cols] when req_pool is set
-    int table_i64;
-    int64_t tb_sr, tb_sc;
-    const void *req_pool;           // [batch]; null = block-table form
-    int req_i64, rtt_cols, num_pages, sanitize;
+    PageMap pages;
     const void *sink;               // [q_heads, d], rows sink_sh apart; null = none
     int sink_dtype;
     int64_t sink_sh;
@@ -52,10 +48,6 @@ struct Params {
     float sm_scale;
 };
 
-__device__ __forceinline__ int64_t load_index(const void *base, int is_i64, int64_t off)
-{
-    return is_i64 ? ((const int64_t *)base)[off] : (int64_t)((const int32_t *)base)[off];
-}
 __device__ __forceinline__ float load_elem(const void *base, int dtype, int64_t off)
 {
     if (dtype == MI_DTYPE_F32) return ((const float *)base)[off];
@@ -99,18 +91,7 @@ __global__ __launch_bounds__(256) void gqa_sparse_decode_kernel(Params p)
         int32_t lb = -1, pg = 0;
         if (i < n_slots) {
             const int64_t l = load_index(p.topk, p.topk_i64, kvh * p.ti_sh + b * p.ti_sb + (int64_t)(s_begin + i) * p.ti_st);
-            if (l >= 0 && l * BS < (int64_t)seq_len) {
-                int64_t page;
-                if (p.req_pool) {
-                    const int64_t req = load_index(p.req_pool, p.req_i64, b);
-                    const int64_t col = min(l * BS, (int64_t)p.rtt_cols - 1);
-                    page = load_index(p.table, p.table_i64, req * p.tb_sr + col * p.tb_sc) / BS;
-                    if (p.sanitize) page = min(max(page, (int64_t)0), (int64_t)p.num_pages - 1);
-                } else {
-                    page = load_index(p.table, p.table_i64, b * p.tb_sr + l * p.tb_sc);
-                }
-                lb = (int32_t)l, pg = (int32_t)page;
-            }
+            if (l >= 0 && l * BS < (int64_t)seq_len) lb = (int32_t)l, pg = (int32_t)page_of(p.pages, b, l, BS);
         }
         s_lb[i] = lb, s_pg[i] = pg;
     }
@@ -266,8 +247,6 @@ __global__ __launch_bounds__(256) void gqa_sparse_decode_kernel(Params p)
     }
 }
 
-static int padded_dim(int d) { return d <= 64 ? 64 : d <= 128 ? 128 : d <= 256 ? 256 : 0; }
-
 template <bool BF16, int DP, int HB>
 static void launch_one(const Params &p, unsigned grid, hipStream_t st)
 {
@@ -278,21 +257,6 @@ static void launch_one(const Params &p, unsigned grid, hipStream_t st)
                                   (int)(tiles + 2 * sizeof(int32_t) * kMaxChunkSlots));
     }
     gqa_sparse_decode_kernel<BF16, DP, HB><<<grid, 256, tiles + 2 * sizeof(int32_t) * p.list_cap, st>>>(p);
-}
-
-template <bool BF16, int HB>
-static void launch_dim(int dp, const Params &p, unsigned grid, hipStream_t st)
-{
-    if (dp == 64) launch_one<BF16, 64, HB>(p, grid, st);
-    else if (dp == 128) launch_one<BF16, 128, HB>(p, grid, st);
-    else launch_one<BF16, 256, HB>(p, grid, st);
-}
-
-static int cus()
-{
-    int d = 0, n = 0;
-    if (hipGetDevice(&d) != hipSuccess) return 256;
-    return (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0) ? n : 256;
 }
 
 }  // namespace mi_gqa_sparse
@@ -330,11 +294,8 @@ extern "C" int mi_gqa_sparse_decode(const void *q, const void *k, const void *v,
                                     int dtype, int num_chunks, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (batch < 0 || q_heads <= 0 || kv_heads <= 0 || q_heads % kv_heads || topk < 0 || max_kv_len < 0) return MI_SGL_EINVAL;
-    if (block_size != 16 && block_size != 32 && block_size != 64 && block_size != 128) return MI_SGL_EINVAL;
+    if (!block_args_ok(block_size, head_dim, dtype, sm_scale)) return MI_SGL_EINVAL;
     const int dp = padded_dim(head_dim);
-    if (head_dim <= 0 || (head_dim % 8) || !dp) return MI_SGL_EINVAL;
-    if (dtype != MI_DTYPE_BF16 && dtype != MI_DTYPE_F16) return MI_SGL_EINVAL;
-    if (!(sm_scale > 0.f)) return MI_SGL_EINVAL;                  // the running maximum is taken before the scaling
     if (sink && sink_dtype != MI_DTYPE_BF16 && sink_dtype != MI_DTYPE_F16 && sink_dtype != MI_DTYPE_F32) return MI_SGL_EINVAL;
     // exactly one page source
     const bool direct = req_to_token != nullptr;
@@ -346,8 +307,8 @@ extern "C" int mi_gqa_sparse_decode(const void *q, const void *k, const void *v,
     if (chunk_slots > kMaxChunkSlots) return MI_SGL_ENOTAPPLICABLE;   // more chunks bring a longer list into reach
     if (batch == 0) return MI_SGL_OK;
     if (!q || !k || !v || !out || !seq_lens || (topk > 0 && !topk_idx)) return MI_SGL_EINVAL;
-    if ((q_stride_h % 8) || (q_stride_b % 8) || (k_stride_row % 8) || (k_stride_blk % 8) || (k_stride_h % 8) || (v_stride_row % 8) ||
-        (v_stride_blk % 8) || (v_stride_h % 8) || (o_stride_h % 4) || (o_stride_b % 4))
+    if (!aligned8({q_stride_h, q_stride_b, k_stride_row, k_stride_blk, k_stride_h, v_stride_row, v_stride_blk, v_stride_h}) ||
+        (o_stride_h % 4) || (o_stride_b % 4))
         return MI_SGL_EINVAL;      // 16-byte loads, 8-byte stores
     if (num_chunks > 1 && (!workspace || ((uintptr_t)workspace & 15) ||
                            workspace_bytes < mi_gqa_sparse_decode_workspace(batch, q_heads, head_dim, num_chunks)))
@@ -355,14 +316,8 @@ extern "C" int mi_gqa_sparse_decode(const void *q, const void *k, const void *v,
     Params p;
     p.q = (const uint16_t *)q, p.k = (const uint16_t *)k, p.v = (const uint16_t *)v, p.out = (uint16_t *)out, p.seq_lens = seq_lens;
     p.topk = topk_idx, p.topk_i64 = topk_is_i64, p.ti_sh = topk_stride_h, p.ti_sb = topk_stride_b, p.ti_st = topk_stride_t;
-    if (direct) {
-        p.table = req_to_token, p.table_i64 = req_to_token_is_i64, p.tb_sr = rtt_stride_r, p.tb_sc = rtt_stride_t;
-        p.req_pool = req_pool_indices, p.req_i64 = req_pool_is_i64;
-    } else {
-        p.table = block_table, p.table_i64 = block_table_is_i64, p.tb_sr = bt_stride_b, p.tb_sc = bt_stride_n;
-        p.req_pool = nullptr, p.req_i64 = 0;
-    }
-    p.rtt_cols = rtt_cols, p.num_pages = num_pages, p.sanitize = sanitize_page_ids;
+    p.pages = make_page_map(block_table, block_table_is_i64, bt_stride_b, bt_stride_n, req_to_token, req_to_token_is_i64, rtt_stride_r,
+                            rtt_stride_t, rtt_cols, req_pool_indices, req_pool_is_i64, num_pages, sanitize_page_ids);
     p.sink = sink, p.sink_dtype = sink_dtype, p.sink_sh = sink_stride_h;
     p.ws_o = (float *)workspace;
     p.ws_ml = p.ws_o ? p.ws_o + (size_t)batch * q_heads * num_chunks * dp : nullptr;
@@ -378,8 +333,7 @@ extern "C" int mi_gqa_sparse_decode(const void *q, const void *k, const void *v,
     if (wgs > 0x7fffffffll) return MI_SGL_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const bool bf16 = dtype == MI_DTYPE_BF16;
-    if (bf16) hpw == 64 ? launch_dim<true, 1>(dp, p, (unsigned)wgs, st) : launch_dim<true, 2>(dp, p, (unsigned)wgs, st);
-    else hpw == 64 ? launch_dim<false, 1>(dp, p, (unsigned)wgs, st) : launch_dim<false, 2>(dp, p, (unsigned)wgs, st);
+    dispatch(bf16, dp, hpw == 64, [&](auto bf, auto d, auto one) { launch_one<bf(), d(), one() ? 1 : 2>(p, (unsigned)wgs, st); });
     if (num_chunks > 1) {
         GqaParams m{};                                            // the merge kernel of gqa_decode.hip on this kernel's partial layout
         m.out = (uint16_t *)out, m.ws_o = p.ws_o, m.ws_ml = p.ws_ml, m.batch = batch, m.q_heads = q_heads, m.kv_heads = kv_heads;

@@ -34,7 +34,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "gqa_common.h"
+#include "block_score_dev.h"
 #include "mi_sgl_kernels.h"
 
 namespace mi_li {
@@ -338,23 +338,8 @@ __global__ __launch_bounds__(kSelThreads) void lightning_select_kernel(Params p)
     while (P < n) P *= 2;
     for (int t = n + tid; t < P; t += kSelThreads) cand[t] = ~0ull;
     __syncthreads();
-    for (int size = 2; size <= P; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < (P >> 1); i += kSelThreads) {
-                const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-                const uint64_t a = cand[lo], c = cand[hi];
-                if ((a > c) == ((lo & size) == 0)) cand[lo] = c, cand[hi] = a;
-            }
-            __syncthreads();
-        }
+    bitonic_sort<kSelThreads>(cand, P);
     for (int t = tid; t < K; t += kSelThreads) orow[t] = t < n ? (int32_t)(uint32_t)cand[t] : -1;
-}
-
-static int cus()
-{
-    int d = 0, n = 0;
-    if (hipGetDevice(&d) != hipSuccess) return 256;
-    return (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0) ? n : 256;
 }
 
 static size_t ws_bound()                                          // MI_LIGHTNING_INDEXER_WS_BYTES lowers (or raises) the bound: tests use it

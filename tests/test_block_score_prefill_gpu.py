@@ -209,6 +209,40 @@ def test_tiling_knobs_change_nothing():
         assert torch.equal(base_i, run_python(g, block_size_q=bsq, qblock_mappings=(None,) * 6))
 
 
+def decode_prefill_pair(B, H, Hkv, D, bs, lens, max_seqblock, topk, dtype, seed):
+    """One problem in both forms: a decode batch (req_to_token form), and the same requests as one query token each at position len - 1."""
+    gen = torch.Generator().manual_seed(seed)
+    used = [-(-n // bs) for n in lens]
+    pages = torch.randperm(sum(used), generator=gen).tolist()
+    k = torch.randn((sum(used), bs, Hkv, D), generator=gen).to(dtype).cuda()
+    q = torch.randn((B, H, D), generator=gen).to(dtype).cuda()
+    rtt = torch.zeros((B, max_seqblock * bs), dtype=torch.int32)
+    for b in range(B):
+        for j in range(used[b]):
+            rtt[b, j * bs:(j + 1) * bs] = pages.pop() * bs + torch.arange(bs)
+    both = dict(q=q, k=k, seq_lens=torch.tensor(lens, dtype=torch.int32).cuda(), req_to_token=rtt.cuda(), max_seqlen=max_seqblock * bs,
+                req_pool_indices=torch.arange(B, dtype=torch.int32).cuda(), block_size=bs, sm_scale=float(D) ** -0.5)
+    decode = dict(both, topk=topk, init_blocks=0, local_blocks=0, max_num_blocks=max_seqblock, num_pages=sum(used))
+    return decode, dict(both, cu_seqlens=torch.arange(B + 1, dtype=torch.int32).cuda()), used
+
+
+@pytest.mark.parametrize("shape,score_types", [
+    ((2, 8, 2, 64, 16, [597, 203], 40, 4, torch.bfloat16), ("max", "lse")),       # 38 and 13 blocks, the last partial: the masked path
+    ((1, 4, 1, 256, 128, [700], 6, 2, torch.float16), ("lse",)),                  # head dim 256: stages of two units
+], ids=["g4_d64_bs16", "d256_bs128"])
+def test_decode_and_prefill_scores_agree(shape, score_types):
+    """The decode and the prefill indexer run one score engine: a block's score is the same bits in both.  Every MFMA output column is its
+    own dot product, the per-lane sum order is the same and the run partition does not enter a block's score.  Blocks behind a request's
+    end are -inf in the prefill form and unwritten in the decode form: not compared."""
+    from test_block_score_gpu import run_capi as run_decode_capi
+    decode, prefill, used = decode_prefill_pair(*shape, seed=11)
+    for st in score_types:
+        _, dec = run_decode_capi(dict(decode, score_type=st))   # [B, H, max_seqblock]
+        pre = run_capi_score(prefill, st)                       # [H, B, max_seqblock]
+        for b, nb in enumerate(used):
+            assert torch.equal(dec[b, :, :nb], pre[:, b, :nb]), (st, b, (dec[b, :, :nb] != pre[:, b, :nb]).nonzero().tolist())
+
+
 # ---- with the attention kernels ------------------------------------------------------------------------------------------------------------
 def dense_causal_ref(c, round_p=None):
     """float64 softmax attention of every token over the keys 0 .. position of its request; round_p: P rounded to that dtype before P.V."""
