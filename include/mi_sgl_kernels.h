@@ -12,6 +12,8 @@
  *   mi_topk_append_local_block <- indexer/flash_block_score_decode.py:1451-1562 (append_local_block_to_topk_idx)
  *   mi_gqa_prefill_block_score, mi_prefill_topk_from_score <- indexer/flash_block_score_prefill.py:21-220,434-557,673-811,865-909
  *                               (flash_prefill_bnsd_score, flash_prefill_bnsd_topk_from_score, flash_prefill_bnsd_with_topk_idx)
+ *   mi_lightning_indexer     <- csrc/lightning_indexer/ (torch.ops.npu.lightning_indexer)
+ *   mi_sparse_attn_sharedkv  <- csrc/sparse_attn_sharedkv/ (torch.ops.npu.sparse_attn_sharedkv)
  *   mi_swiglu_quant          <- activation/swiglu_quant.py:8-127     (_swiglu_quant_kernel / swiglu_quant)
  *   mi_add_rmsnorm_bias      <- norm/add_rmsnorm_bias.py:8-147        (add_rmsnorm_bias_kernel / add_rmsnorm_bias)
  *                               norm/add_rmsnorm_bias.py:150-232      (add_gemma_rms_norm)
@@ -270,6 +272,44 @@ int mi_lightning_indexer(const void *query, const void *key, const void *weights
                          int64_t s2_capacity, int block_size, int64_t bt_stride_b, int64_t q_stride_0, int64_t q_stride_1, int64_t q_stride_h,
                          int64_t w_stride_0, int64_t w_stride_1, int64_t k_stride_blk, int64_t k_stride_row, int sparse_count, int sparse_mode,
                          int dtype, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- window + token-sparse shared-KV attention (csrc/sparse_attn_sharedkv/: torch.ops.npu.sparse_attn_sharedkv) -------------------------
+ * 64-head MQA over one shared 512-wide latent that is both K and V: the consumer of the lightning indexer's key indices.  Rows: layout_q
+ * BSND: q [batch, s1, 64, 512] (strides q_stride_b, q_stride_s, q_stride_h, 1), tokens = batch * s1, S1_b = seqused_q[b] clamped to [0, s1]
+ * (NULL: s1), rows at or behind it are written as zeros; TND: q [tokens, 64, 512] (q_stride_s per token, q_stride_b unused), cu_seqlens_q
+ * [batch + 1] from 0, S1_b = cu[b + 1] - cu[b], searched on the device; tokens at or behind cu[batch] are written as zeros.  out has q's
+ * shape (o_stride_*).  Per token i of sequence b, with L = seqused_kv[b] (clamped to ori_columns * ori_block) and position
+ * p = L - S1_b + i; p < 0 or L <= 0: a row of zeros.
+ *   window part   keys n in [max(p - ori_win_left, 0), min(p + ori_win_right, L - 1)] of ori_kv [pages, ori_block, 1, 512] (ori_stride_blk per
+ *                 page, rows contiguous) through ori_block_table [batch, ori_columns] (ori_bt_stride);
+ *   compressed part (cmp_kv != NULL)  limit = (p + 1) / cmp_ratio, clamped to cmp_columns * cmp_block.  cmp_sparse_indices == NULL: keys
+ *                 j in [0, limit) of cmp_kv [pages, cmp_block, 1, 512] through cmp_block_table [batch, cmp_columns]; otherwise the token's
+ *                 sparse_count slots (BSND: [batch, s1, 1, K] with idx_stride_b, idx_stride_s; TND: [tokens, 1, K] with idx_stride_s), EVERY
+ *                 slot judged on its own: it counts iff 0 <= idx < limit, wherever it stands, and a duplicate counts twice (the reference
+ *                 reads the first min(K, limit) slots and stops at a negative one; on lists of valid entries first, then -1, both agree);
+ *   softmax       s = (q . k) * softmax_scale in fp32, ONE softmax over both parts started from m = sinks[h], l = 1: a virtual key of logit
+ *                 sinks[h] (fp32 [64], not scaled) and value 0; P rounded to the KV dtype before P.V, l summed in fp32, out rounded once.
+ *                 P is formed against a whole-number reference in the log2 domain, so its rounding does not depend on num_splits.
+ * Table entries and index slots of positions outside a token's list are never read, nor is any row it does not attend to.
+ * The list is cut into num_splits pieces per token (0 = choose from tokens, the list bound and the CU count; nothing is read back, so the
+ * call is capturable in a graph); with more than one piece `workspace` of mi_sparse_attn_sharedkv_workspace() bytes holds fp32 partials
+ * that a second launch merges.  list_bound = min(ori_win_left + ori_win_right + 1, ori_columns * ori_block) + (cmp_sparse_indices ?
+ * sparse_count : cmp_kv ? cmp_columns * cmp_block : 0).  The workspace query is host arithmetic (256 CUs when no device answers).
+ * LIMITS (MI_SGL_EINVAL beyond them, nothing launched or written): heads = 64, head_dim = 512; dtype BF16 / F16 (q, ori_kv, cmp_kv alike);
+ * block sizes multiples of 16 up to 1024; cmp_ratio 4 / 128 with cmp_kv (ignored without); 1 <= sparse_count <= 2048; window sizes >= 0;
+ * softmax_scale >= 0; 0 <= num_splits <= 64; strides of q / out / caches multiples of 8 elements, innermost dimension contiguous.
+ * batch = 0 or tokens = 0: MI_SGL_OK without a launch. */
+#define MI_SSK_Q_BSND 0
+#define MI_SSK_Q_TND 1
+size_t mi_sparse_attn_sharedkv_workspace(int64_t tokens, int64_t list_bound, int num_splits);
+int mi_sparse_attn_sharedkv(const void *q, const void *ori_kv, const void *cmp_kv, void *out, const float *sinks,
+                            const int32_t *cmp_sparse_indices, const int32_t *ori_block_table, const int32_t *cmp_block_table,
+                            const int32_t *cu_seqlens_q, const int32_t *seqused_q, const int32_t *seqused_kv, int layout_q, int batch,
+                            int s1, int64_t tokens, int heads, int head_dim, int ori_block, int ori_columns, int cmp_block, int cmp_columns,
+                            int sparse_count, int64_t q_stride_b, int64_t q_stride_s, int64_t q_stride_h, int64_t o_stride_b,
+                            int64_t o_stride_s, int64_t o_stride_h, int64_t idx_stride_b, int64_t idx_stride_s, int64_t ori_stride_blk,
+                            int64_t cmp_stride_blk, int64_t ori_bt_stride, int64_t cmp_bt_stride, float softmax_scale, int cmp_ratio, int ori_win_left, int ori_win_right, int dtype,
+                            int num_splits, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- SwiGLU + per-row INT8 quantisation (swiglu_quant.py:87-127) -------------------------------------------------
  * x [rows, cols] (cols = 2I; gate = x[:, :I], up = x[:, I:]); only the first `total` rows are processed, where total =

@@ -631,6 +631,120 @@ at::Tensor lightning_indexer(const at::Tensor &query, const at::Tensor &key, con
     return out;
 }
 
+// csrc/sparse_attn_sharedkv/op_host/sparse_attn_sharedkv.cpp:49-200 (checks: the same file :60-114 and op_host/sparse_attn_sharedkv_tiling.cpp
+// :1096-1257, :1406-1410, whose wording the messages keep where they have one): window + token-sparse attention over a shared 512-wide
+// latent, the consumer of lightning_indexer's indices (csrc/kernels/sparse_sharedkv.hip; semantics in include/mi_sgl_kernels.h).  Returns
+// (attention_out = empty_like(q) with every row written, an empty fp32 softmax_lse).  metadata (the reference's per-core schedule) is checked
+// when given and never read; cu_seqlens_ori_kv / cu_seqlens_cmp_kv belong to the non-paged layouts and are ignored under PA_ND.
+std::tuple<at::Tensor, at::Tensor> sparse_attn_sharedkv(
+    const at::Tensor &q, const std::optional<at::Tensor> &ori_kv, const std::optional<at::Tensor> &cmp_kv,
+    const std::optional<at::Tensor> &ori_sparse_indices, const std::optional<at::Tensor> &cmp_sparse_indices,
+    const std::optional<at::Tensor> &ori_block_table, const std::optional<at::Tensor> &cmp_block_table,
+    const std::optional<at::Tensor> &cu_seqlens_q, const std::optional<at::Tensor> &cu_seqlens_ori_kv,
+    const std::optional<at::Tensor> &cu_seqlens_cmp_kv, const std::optional<at::Tensor> &seqused_q, const std::optional<at::Tensor> &seqused_kv,
+    const std::optional<at::Tensor> &sinks, const std::optional<at::Tensor> &metadata, double softmax_scale, int64_t cmp_ratio,
+    int64_t ori_mask_mode, int64_t cmp_mask_mode, int64_t ori_win_left, int64_t ori_win_right, c10::string_view layout_q,
+    c10::string_view layout_kv, bool return_softmax_lse)
+{
+    const c10::DeviceGuard device_guard(q.device());   // launches and the current stream follow the tensor's GPU
+    const bool tnd = layout_q == "TND";
+    TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "sparse_attn_sharedkv: q must be float16 or bfloat16");
+    TORCH_CHECK(layout_q == "BSND" || tnd, "sparse_attn_sharedkv: layout_q must be 'BSND' or 'TND'");
+    TORCH_CHECK((!tnd && q.dim() == 4) || (tnd && q.dim() == 3), "sparse_attn_sharedkv: q rank does not match layout_q");
+    TORCH_CHECK(ori_kv.has_value(), "sparse_attn_sharedkv: ori_kv is required");
+    TORCH_CHECK(sinks.has_value(), "sparse_attn_sharedkv: sinks is required");
+    TORCH_CHECK(layout_kv == "PA_ND", "sparse_attn_sharedkv: this port currently supports layout_kv='PA_ND' only");
+    TORCH_CHECK(!return_softmax_lse, "sparse_attn_sharedkv: return_softmax_lse=true is not supported");
+    TORCH_CHECK(!ori_sparse_indices.has_value(),
+                "sparse_attn_sharedkv: ori_sparse_indices (a second gather over the original cache) is not supported here");
+    TORCH_CHECK(ori_block_table.has_value(), "sparse_attn_sharedkv: ori_block_table is required for PA_ND");
+    TORCH_CHECK(seqused_kv.has_value(), "sparse_attn_sharedkv: seqused_kv is required for PA_ND");
+    TORCH_CHECK(!cmp_kv.has_value() || cmp_block_table.has_value(), "sparse_attn_sharedkv: cmp_block_table is required when cmp_kv is present");
+    TORCH_CHECK(!cmp_sparse_indices.has_value() || cmp_kv.has_value(),
+                "sparse_attn_sharedkv: cmp_kv is required when cmp_sparse_indices is present");
+    TORCH_CHECK(!tnd || cu_seqlens_q.has_value(), "sparse_attn_sharedkv: cu_seqlens_q is required for TND query layout");
+    TORCH_CHECK(tnd || !cu_seqlens_q.has_value(), "sparse_attn_sharedkv: cu_seqlens_q must be None for BSND query layout");
+    TORCH_CHECK(ori_win_left >= 0 && ori_win_right >= 0, "sparse_attn_sharedkv: window sizes must be non-negative");
+    TORCH_CHECK(ori_win_left <= INT32_MAX && ori_win_right <= INT32_MAX, "sparse_attn_sharedkv: integer attributes exceed the supported range");
+    TORCH_CHECK(softmax_scale >= 0.0 && softmax_scale < HUGE_VAL, "sparse_attn_sharedkv: softmax_scale must be non-negative");
+    TORCH_CHECK(ori_kv->scalar_type() == q.scalar_type(), "sparse_attn_sharedkv: ori_kv dtype must match q dtype");
+    TORCH_CHECK(!cmp_kv.has_value() || cmp_kv->scalar_type() == q.scalar_type(), "sparse_attn_sharedkv: cmp_kv dtype must match q dtype");
+    TORCH_CHECK(sinks->scalar_type() == at::kFloat, "sparse_attn_sharedkv: sinks must be float32");
+    TORCH_CHECK(!metadata.has_value() || (metadata->scalar_type() == at::kInt && metadata->numel() == 1024),
+                "sparse_attn_sharedkv: metadata must be int32 with 1024 elements");
+    TORCH_CHECK(ori_mask_mode == 4, "sparse_attn_sharedkv: ori_mask_mode only supports 4");
+    TORCH_CHECK(cmp_mask_mode == 3, "sparse_attn_sharedkv: cmp_mask_mode only supports 3");
+    const int64_t heads = q.size(tnd ? 1 : 2), D = q.size(tnd ? 2 : 3);
+    TORCH_CHECK(heads == 64, "sparse_attn_sharedkv: the initial port supports exactly 64 query heads");
+    TORCH_CHECK(D == 512, "sparse_attn_sharedkv: head dim of q only supports 512");
+    auto int32 = [](const std::optional<at::Tensor> &t, const char *name) {
+        TORCH_CHECK(!t.has_value() || t->scalar_type() == at::kInt, name, " must be int32");
+    };
+    int32(cmp_sparse_indices, "cmp_sparse_indices"), int32(ori_block_table, "ori_block_table"), int32(cmp_block_table, "cmp_block_table");
+    int32(cu_seqlens_q, "cu_seqlens_q"), int32(cu_seqlens_ori_kv, "cu_seqlens_ori_kv"), int32(cu_seqlens_cmp_kv, "cu_seqlens_cmp_kv");
+    int32(seqused_q, "seqused_q"), int32(seqused_kv, "seqused_kv");
+    auto same_device = [&](const std::optional<at::Tensor> &t, const char *name) {
+        TORCH_CHECK(!t.has_value() || t->device() == q.device(), name, " must be on the same device as q");
+    };
+    same_device(ori_kv, "ori_kv"), same_device(cmp_kv, "cmp_kv"), same_device(cmp_sparse_indices, "cmp_sparse_indices");
+    same_device(ori_block_table, "ori_block_table"), same_device(cmp_block_table, "cmp_block_table"), same_device(cu_seqlens_q, "cu_seqlens_q");
+    same_device(seqused_q, "seqused_q"), same_device(seqused_kv, "seqused_kv"), same_device(sinks, "sinks");
+    auto paged = [&](const at::Tensor &kv, const at::Tensor &table, const char *name) {
+        TORCH_CHECK(kv.dim() == 4 && kv.size(2) == 1 && kv.size(3) == D, "sparse_attn_sharedkv: ", name, " must be [pages, block, 1, 512]");
+        TORCH_CHECK(kv.size(1) > 0 && kv.size(1) <= 1024 && kv.size(1) % 16 == 0, "sparse_attn_sharedkv: block size of ", name,
+                    " must be a multiple of 16 and belong to (0, 1024]");
+        TORCH_CHECK(kv.stride(3) == 1 && kv.stride(1) == D && kv.stride(0) % 8 == 0, "sparse_attn_sharedkv: rows of ", name,
+                    " must be contiguous and its page stride a multiple of 8 elements");
+        TORCH_CHECK(table.dim() == 2 && table.size(1) > 0, "sparse_attn_sharedkv: the block table of ", name, " must be [batch, columns]");
+    };
+    paged(*ori_kv, *ori_block_table, "ori_kv");
+    if (cmp_kv.has_value()) {
+        paged(*cmp_kv, *cmp_block_table, "cmp_kv");
+        TORCH_CHECK(cmp_ratio == 4 || cmp_ratio == 128, "sparse_attn_sharedkv: cmp_ratio only supports 4 or 128 when cmp_kv is present");
+    }
+    TORCH_CHECK(sinks->numel() == heads, "sparse_attn_sharedkv: sinks must hold one value per query head");
+    const int64_t B = tnd ? cu_seqlens_q->numel() - 1 : q.size(0), S1 = tnd ? 1 : q.size(1), tokens = tnd ? q.size(0) : B * S1;
+    TORCH_CHECK(B >= 0 && B <= INT32_MAX && S1 <= INT32_MAX, "sparse_attn_sharedkv: batch size");
+    TORCH_CHECK(seqused_kv->numel() == B, "sparse_attn_sharedkv: seqused_kv's dimension should be equal to ", B);
+    TORCH_CHECK(!seqused_q.has_value() || seqused_q->numel() == B, "sparse_attn_sharedkv: seqused_q's dimension should be equal to ", B);
+    TORCH_CHECK(ori_block_table->size(0) == B && (!cmp_block_table.has_value() || cmp_block_table->size(0) == B),
+                "sparse_attn_sharedkv: dim 0 of the block tables must be the batch size");
+    int64_t K = 0;
+    if (cmp_sparse_indices.has_value()) {
+        const at::Tensor &ix = *cmp_sparse_indices;
+        TORCH_CHECK(ix.dim() == q.dim() && ix.size(q.dim() - 2) == 1 && ix.size(0) == q.size(0) && (tnd || ix.size(1) == S1),
+                    "sparse_attn_sharedkv: cmp_sparse_indices must be [B, S1, 1, K] (BSND) or [T, 1, K] (TND)");
+        K = ix.size(q.dim() - 1);
+        TORCH_CHECK(K >= 1 && K <= 2048, "sparse_attn_sharedkv: the sparse count K of cmp_sparse_indices must belong to [1, 2048], but now is ", K);
+    }
+    TORCH_CHECK(q.stride(q.dim() - 1) == 1 && q.stride(q.dim() - 2) % 8 == 0, "sparse_attn_sharedkv: q's innermost dimension must be contiguous");
+
+    at::Tensor attention_out = at::empty_like(q);
+    at::Tensor softmax_lse = at::empty({0}, q.options().dtype(at::kFloat));
+    if (B == 0 || tokens == 0) return {attention_out, softmax_lse};
+    auto contig = [](const std::optional<at::Tensor> &t) { return t.has_value() ? std::optional<at::Tensor>(t->contiguous()) : std::nullopt; };
+    auto rows_contig = [&](const std::optional<at::Tensor> &t) { return t.has_value() && t->stride(t->dim() - 1) != 1 ? contig(t) : t; };
+    const std::optional<at::Tensor> cu = contig(cu_seqlens_q), sq = contig(seqused_q), skv = contig(seqused_kv);
+    const std::optional<at::Tensor> obt = rows_contig(ori_block_table), cbt = rows_contig(cmp_block_table), ix = rows_contig(cmp_sparse_indices);
+    const at::Tensor sk = sinks->contiguous();
+    auto i32 = [](const std::optional<at::Tensor> &t) { return t.has_value() ? t->data_ptr<int>() : nullptr; };
+    const int64_t win = ori_win_left + ori_win_right + 1, ori_cap = obt->size(1) * ori_kv->size(1);
+    const int64_t list_bound = std::min(win, ori_cap) + (ix.has_value() ? K : cmp_kv.has_value() ? cbt->size(1) * cmp_kv->size(1) : 0);
+    const size_t wsb = mi_sparse_attn_sharedkv_workspace(tokens, list_bound, 0);
+    at::Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 16)}, at::dtype(at::kByte).device(q.device()));
+    const at::Tensor &o = attention_out;
+    const int rc = mi_sparse_attn_sharedkv(
+        q.data_ptr(), ori_kv->data_ptr(), cmp_kv.has_value() ? cmp_kv->data_ptr() : nullptr, o.data_ptr(), sk.data_ptr<float>(), i32(ix),
+        i32(obt), i32(cbt), i32(cu), i32(sq), i32(skv), tnd ? MI_SSK_Q_TND : MI_SSK_Q_BSND, (int)B, (int)S1, tokens, (int)heads, (int)D,
+        (int)ori_kv->size(1), (int)obt->size(1), cmp_kv.has_value() ? (int)cmp_kv->size(1) : 0, cbt.has_value() ? (int)cbt->size(1) : 0, (int)K,
+        tnd ? 0 : q.stride(0), tnd ? q.stride(0) : q.stride(1), q.stride(q.dim() - 2), tnd ? 0 : o.stride(0), tnd ? o.stride(0) : o.stride(1),
+        o.stride(o.dim() - 2), ix.has_value() && !tnd ? ix->stride(0) : 0, ix.has_value() ? ix->stride(tnd ? 0 : 1) : 0, ori_kv->stride(0),
+        cmp_kv.has_value() ? cmp_kv->stride(0) : 0, obt->stride(0), cbt.has_value() ? cbt->stride(0) : 0, (float)softmax_scale, (int)cmp_ratio,
+        (int)ori_win_left, (int)ori_win_right, dtype_code(q), 0, ws.data_ptr(), wsb, cur_stream());
+    TORCH_CHECK(rc == 0, "mi_sparse_attn_sharedkv failed with code ", rc, " (strides of q / out multiples of 8 elements)");
+    return {attention_out, softmax_lse};
+}
+
 // SwiGLU + per-row INT8 quantisation; same arguments / returns as swiglu_quant (activation/swiglu_quant.py:87-127).
 std::tuple<at::Tensor, at::Tensor> swiglu_quant(const at::Tensor &x, const at::Tensor &group_list, int64_t group_list_type,
                                                 bool need_quant, bool do_limit, double limit)
@@ -1348,6 +1462,16 @@ TORCH_LIBRARY_FRAGMENT(npu, m)
         "Tensor? actual_seq_lengths_key=None, Tensor? block_table=None, "
         "str? layout_query=None, str? layout_key=None, "
         "int? sparse_count=None, int? sparse_mode=None) -> Tensor");
+    m.def(
+        "sparse_attn_sharedkv(Tensor q, *, Tensor? ori_kv=None, Tensor? cmp_kv=None, "
+        "Tensor? ori_sparse_indices=None, Tensor? cmp_sparse_indices=None, "
+        "Tensor? ori_block_table=None, Tensor? cmp_block_table=None, "
+        "Tensor? cu_seqlens_q=None, Tensor? cu_seqlens_ori_kv=None, "
+        "Tensor? cu_seqlens_cmp_kv=None, Tensor? seqused_q=None, Tensor? seqused_kv=None, "
+        "Tensor? sinks=None, Tensor? metadata=None, float softmax_scale=0, int cmp_ratio=0, "
+        "int ori_mask_mode=4, int cmp_mask_mode=3, int ori_win_left=128, int ori_win_right=0, "
+        "str layout_q='BSND', str layout_kv='PA_ND', "
+        "bool return_softmax_lse=False) -> (Tensor, Tensor)");
     m.def("attn_residual_mix(Tensor prefix_sum, Tensor bank, int num_valid_blocks, Tensor combined_weight, float variance_epsilon) -> Tensor");
     m.def("mul_add(Tensor routed_input, Tensor shared_input, float scaling_factor) -> Tensor");
     m.def("zero_experts_compute_identity(Tensor(a!) expert_indices, Tensor(b!) expert_scales, int num_experts, Tensor hidden_states, "
@@ -1391,6 +1515,7 @@ TORCH_LIBRARY_IMPL(npu, CUDA, m)
     m.impl("gqa_prefill_block_score", TORCH_FN(sglang::npu_kernel::gqa_prefill_block_score));
     m.impl("prefill_topk_from_score", TORCH_FN(sglang::npu_kernel::prefill_topk_from_score));
     m.impl("lightning_indexer", TORCH_FN(sglang::npu_kernel::lightning_indexer));
+    m.impl("sparse_attn_sharedkv", TORCH_FN(sglang::npu_kernel::sparse_attn_sharedkv));
     m.impl("attn_residual_mix", TORCH_FN(sglang::npu_kernel::attn_residual_mix));
     m.impl("mul_add", TORCH_FN(sglang::npu_kernel::mul_add));
     m.impl("zero_experts_compute_identity", TORCH_FN(sglang::npu_kernel::zero_experts_compute_identity));
