@@ -1,5 +1,7 @@
-// Shared pieces of the two MLA decode kernels (mla_decode.hip: 64 heads per workgroup on 16x16x32 MFMAs;
-// mla_decode_wide.hip: 128 heads per workgroup on 32x32x16 MFMAs).
+// Shared pieces of the MLA latent kernels: the parameter block, the MFMA / pack / output-conversion wrappers, the per-tile block-table
+// addressing, the wide kernels' launchers and the exact slow path.  Users: mla_decode.hip (64 heads per workgroup on 16x16x32 MFMAs, 64-key
+// tiles; also the merge kernel and the C entry points), mla_decode_wide.hip / mla_decode_wide8.hip / mla_decode_wide8s.hip (128 heads per
+// workgroup on 32x32x16 MFMAs, 32-key tiles) and, through latent_tile_dev.h (the 64-head tile engine), sparse_sharedkv.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -90,7 +92,7 @@ __device__ __forceinline__ uint16_t cvt_out(float f)
 
 // Per-tile row addressing.  Lane l owns key l of a tile: tile_rows() turns its token index into byte offsets of the
 // key's nope / rope rows (one block-table load per lane per tile, issued a whole tile ahead of its use so the load
-// latency never sits in front of the LDS-DMA).  issue_tile() then fetches row addresses from lanes with readlane /
+// latency never sits in front of the LDS-DMA).  The fill then fetches row addresses from lanes with readlane /
 // shuffle, so no vector-memory wait separates consecutive DMA instructions.
 struct TileRows {
     int64_t nope, rope;     // element offsets into k_nope / k_rope

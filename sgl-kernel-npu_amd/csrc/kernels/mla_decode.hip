@@ -1,4 +1,5 @@
-// Paged MLA decode attention for gfx950 (MI355X), bf16 / fp16.
+// Paged MLA decode attention for gfx950 (MI355X), bf16 / fp16: the 64-heads-per-workgroup kernel, the merge of the flash-decoding partials
+// and the C entry points (kv groups of more than 64 heads run the wide kernels, mla_decode_wide*.hip, launched from here).
 // Replaces the reference Triton kernel _paged_mla_fwd_kernel / decode_mla
 // (python/sgl_kernel_npu/sgl_kernel_npu/attention/decode_attention.py:5-230): same math (scores in fp32, online softmax,
 // P rounded to the KV dtype, V aliases K_nope, out = acc / l), different schedule.
@@ -6,17 +7,20 @@
 // MI355X design (BASELINE C4: B=128, 128 q-heads sharing one latent KV head, D = 512 + 64, seqlen 4096)
 //  * arithmetic intensity ~242 FLOP/B sits under the HBM/MFMA ridge (~400): the KV stream must be read from HBM exactly
 //    once.  A workgroup is 4 waves x 16 heads, ONE wave per SIMD so each wave owns the whole 512-entry register file
-//    (128 accumulators + 72 resident Q^T registers leave room for deep operand prefetch -- with two waves per SIMD the
-//    compiler serialised every ds_read behind its MFMA).  The two 64-head workgroups of a sequence get adjacent
+//    (128 accumulators for all 512 output dims + 72 resident Q^T registers leave room for deep operand prefetch -- with two
+//    waves per SIMD the compiler serialised every ds_read behind its MFMA).  The two 64-head workgroups of a sequence get adjacent
 //    workgroup ids on the SAME XCD (id -> XCD is id % 8), so the second reader of a KV tile hits that XCD's L2 and HBM
 //    still sees each tile once (the reference launches one program per 16 heads and re-reads KV 8 times);
-//  * KV tiles of 64 keys go global -> LDS by LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave-instruction, no VGPR
-//    staging), double buffered (2 x 74 KB of the 160 KB LDS), ONE barrier per tile; any page_size works because every
-//    key row is addressed through the block table individually;
+//  * KV tiles of 64 keys go global -> LDS by LDS-DMA (1 KiB per wave-instruction, no VGPR staging), one of a wave's 18 pieces
+//    issued behind each of the 18 QK k-steps of the tile before, double buffered (2 x 74 KB of the 160 KB LDS), ONE barrier
+//    per tile; any page_size works because every key row is addressed through the block table individually;
 //  * both GEMMs run transposed so nothing is shuffled between them: S^T[key, head] = K · Q^T (A = K rows from LDS via
 //    ds_read_b128, B = Q^T fragments resident in 72 VGPRs) and O^T[d, head] += V^T · P^T (A = V^T through the LDS
 //    transpose read ds_read_b64_tr_b16, B = P^T which IS the S^T accumulator layout, packed to bf16 in place);
-//    v_mfma_f32_16x16x32_{bf16,f16}; softmax statistics are one value per lane (lane = head);
+//    v_mfma_f32_16x16x32_{bf16,f16}; softmax statistics are one value per lane (lane = head).  The tile schedule -- fill
+//    primitive, QK pipeline, softmax step, P.V, the two finishes -- is latent_tile_dev.h, shared with sparse_sharedkv.hip;
+//    this file holds what is MLA's own: work decode (uniform splits or the planned list), block-table addressing, the
+//    rope part of a tile and the mask of the tile that crosses seq_len;
 //  * nope rows are padded to 1056 B (conflict-free ds_read_b128 across the 16 keys of an MFMA operand); the 128-B rope
 //    rows are XOR-swizzled by choosing which global chunk each LDS-DMA lane fetches;
 //  * flash-decoding split over the KV range fills the 256 CUs when batch < 256 (C4: 2 splits -> 256 workgroups); a small
@@ -30,159 +34,36 @@
 #include "mi_sgl_kernels.h"
 #include <stdlib.h>
 
-#include "mla_common.h"
-
-// Tile fill: 0 = LDS-DMA (global_load_lds) with one 1-KiB piece issued per QK k-step (default, fastest);
-// 1 = register-staged (global_load_dwordx4 -> VGPR -> ds_write_b128), kept as the measured alternative.
-#ifndef MLA_STAGE
-#define MLA_STAGE 0
-#endif
+#include "gqa_common.h"      // cus(), aligned8()
+#include "latent_tile_dev.h"
 
 namespace mi_sgl {
 
-// Reductions across the four 16-lane rows of a wave through v_permlane16_swap / v_permlane32_swap (VALU) instead of ds_bpermute (an LDS
-// round trip each).  swap16(x): {rows 0,0,2,2 | rows 1,1,3,3} of x; swap32(x): {lower half twice | upper half twice}.  Sums and maxima of
-// the two parts are the xor-16 / xor-32 butterfly steps (same two operands in every lane: bit-identical to the shuffle form).
-struct RowPair {
-    float a, b;
-};
-__device__ __forceinline__ RowPair swap16(float x)
-{
-    typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-    const unsigned u = __float_as_uint(x);
-    const u32x2v r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    return RowPair{__uint_as_float(r[0]), __uint_as_float(r[1])};
-}
-__device__ __forceinline__ RowPair swap32(float x)
-{
-    typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-    const unsigned u = __float_as_uint(x);
-    const u32x2v r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return RowPair{__uint_as_float(r[0]), __uint_as_float(r[1])};
-}
-__device__ __forceinline__ float max_over_rows(float x)
-{
-    const RowPair p = swap16(x);
-    const RowPair q = swap32(fmaxf(p.a, p.b));
-    return fmaxf(q.a, q.b);
-}
-__device__ __forceinline__ float sum_over_rows(float x)
-{
-    const RowPair p = swap16(x);
-    const RowPair q = swap32(p.a + p.b);
-    return q.a + q.b;
-}
-
 constexpr int kBufBytes = kTile * kNopeStride + kTile * kRopeStride;   // 74752
-#ifndef MLA_QK_AHEAD
-#define MLA_QK_AHEAD 3
-#endif
-#ifndef MLA_WAVES
-#define MLA_WAVES 4
-#endif
-constexpr int kMaxWaves = MLA_WAVES;
-// MLA_WAVES == 4: one wave per SIMD, each owns 16 heads x all 512 output dims.
-// MLA_WAVES == 8: two waves per SIMD; the pair (w, w+4) shares 16 heads, both compute S (the 72 QK MFMAs are duplicated)
-//                 and each accumulates half of the 512 output dims (64 accumulator registers instead of 128), so a wave
-//                 fits 256 registers WITH operand prefetch and the SIMD always has a second wave to issue from.
-constexpr int kDSplit = kMaxWaves / 4;
-constexpr int kHeadWaves = 4;
-constexpr bool kDmaInterleaved = !MLA_STAGE && MLA_WAVES == 4;   // 18 DMA pieces per wave per tile = 18 QK k-steps
-constexpr int kHeadsPerBlock = kHeadWaves * 16;
-constexpr int kAccTiles = 32 / kDSplit;
+constexpr int kHeadsPerBlock = 64;
 
-// LDS-DMA through inline asm: lane l moves 16 B from its own address to dst + 16 l (M0 = wave-uniform LDS destination).  With the
-// builtin the compiler put an `s_waitcnt vmcnt(0)` behind EVERY piece (it cannot tell which later ds_read the DMA might feed), i.e. one
-// memory round trip per QK k-step; the only wait these requests need is the explicit one at the top of the tile loop.  The compiler's
-// own waits (block-table loads, Q^T) stay correct: requests complete in order, so extra ones in flight only make them conservative.
-__device__ __forceinline__ void dma16_row(const uint8_t *dst_lds, const void *vaddr)
+// One of the 18 DMA instructions a wave contributes to a tile: pieces 0..15 are nope rows wave + 4*idx (issue_nope_row), pieces 16..17 the
+// rope blocks wave + 4*(idx - 16), 8 keys x 128 B each with the XOR swizzle on the source side.  nope = lane's byte address of its key's
+// nope row, rope = lane's element offset of its key's rope row.
+__device__ __forceinline__ int64_t nope_addr(const MlaParams &p, const TileRows &rows) { return (int64_t)(uintptr_t)p.k_nope + 2 * rows.nope; }
+__device__ __forceinline__ void issue_rope_block(const MlaParams &p, int64_t rope, uint8_t *buf, int j, int lane)
 {
-    const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)dst_lds);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(dst), "v"(vaddr) : "memory");
+    const int key = j * 8 + (lane >> 3);
+    const int chunk = (lane & 7) ^ (key & 7);
+    const uint16_t *src = p.k_rope + lane_i64(rope, key);
+    dma_row(buf + kTile * kNopeStride + j * 8 * kRopeStride, src + chunk * 8);
 }
-
-// issue the LDS-DMA of one KV tile into `buf`; the 72 wave-instructions are dealt round-robin to the waves
-__device__ __forceinline__ void issue_tile(const MlaParams &p, const TileRows &rows, uint8_t *buf, int wave, int nwaves, int lane)
+__device__ __forceinline__ void issue_piece(const MlaParams &p, int64_t nope, int64_t rope, uint8_t *buf, int wave, int lane, int idx)
 {
-    for (int i = wave; i < kTile; i += nwaves) {       // one key row (1 KiB of nope) per instruction; i is wave-uniform
-        const int lo = __builtin_amdgcn_readlane((int)(rows.nope & 0xFFFFFFFFll), i);
-        const int hi = __builtin_amdgcn_readlane((int)(rows.nope >> 32), i);
-        const uint16_t *src = p.k_nope + (((int64_t)hi << 32) | (uint32_t)lo);
-        dma16_row(buf + i * kNopeStride, src + lane * 8);
-    }
-    for (int j = wave; j < kTile / 8; j += nwaves) {   // 8 keys x 128 B of rope per instruction
-        const int key = j * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ (key & 7);       // XOR swizzle on the source side
-        const uint16_t *src = p.k_rope + lane_i64(rows.rope, key);
-        dma16_row(buf + kTile * kNopeStride + j * 8 * kRopeStride, src + chunk * 8);
-    }
-}
-
-// one of the 18 DMA instructions a wave contributes to a tile (4-wave build): pieces 0..15 are nope rows wave + 4*idx,
-// pieces 16..17 are the rope blocks wave + 4*(idx - 16).  Lets the caller spread the issue over its MFMA stream.
-__device__ __forceinline__ void issue_piece(const MlaParams &p, const TileRows &rows, uint8_t *buf, int wave, int lane, int idx)
-{
-    if (idx < 16) {
-        const int i = wave + 4 * idx;
-        const int lo = __builtin_amdgcn_readlane((int)(rows.nope & 0xFFFFFFFFll), i);
-        const int hi = __builtin_amdgcn_readlane((int)(rows.nope >> 32), i);
-        const uint16_t *src = p.k_nope + (((int64_t)hi << 32) | (uint32_t)lo);
-        dma16_row(buf + i * kNopeStride, src + lane * 8);
-    } else {
-        const int j = wave + 4 * (idx - 16);
-        const int key = j * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ (key & 7);
-        const uint16_t *src = p.k_rope + lane_i64(rows.rope, key);
-        dma16_row(buf + kTile * kNopeStride + j * 8 * kRopeStride, src + chunk * 8);
-    }
-}
-
-// Register-staged tile fill (MLA_STAGE == 1, 4-wave build): global_load_dwordx4 -> VGPR -> ds_write_b128 in two halves of
-// 9 x 16 B per thread.  LDS-DMA turned out to be capped near 30 GB/s per CU on this part and to back-pressure the
-// issuing (= computing) waves, so fill time added to compute time instead of hiding under it; plain vector loads retire
-// asynchronously at the L1 rate (64 B/clk/CU).
-struct StageRegs {
-    u32x4 v[9];
-};
-
-__device__ __forceinline__ void stage_load(const MlaParams &p, const TileRows &rows, int half, int wave, int lane, StageRegs &st)
-{
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-        const int i = half * 9 + j;
-        if (i < 16) {                                    // nope: row 4i + wave, 16-B column `lane`
-            const int key = 4 * i + wave;
-            const int lo = __builtin_amdgcn_readlane((int)(rows.nope & 0xFFFFFFFFll), key);
-            const int hi = __builtin_amdgcn_readlane((int)(rows.nope >> 32), key);
-            st.v[j] = *(const u32x4 *)(p.k_nope + (((int64_t)hi << 32) | (uint32_t)lo) + lane * 8);
-        } else {                                         // rope: 8 keys x 8 chunks per wave-instruction
-            const int r = (i - 16) * 256 + wave * 64 + lane;
-            const int key = r >> 3;
-            st.v[j] = *(const u32x4 *)(p.k_rope + lane_i64(rows.rope, key) + (r & 7) * 8);
-        }
-    }
-}
-
-__device__ __forceinline__ void stage_store(uint8_t *buf, int half, int wave, int lane, const StageRegs &st)
-{
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-        const int i = half * 9 + j;
-        if (i < 16) {
-            *(u32x4 *)(buf + (4 * i + wave) * kNopeStride + lane * 16) = st.v[j];
-        } else {
-            const int r = (i - 16) * 256 + wave * 64 + lane;
-            const int key = r >> 3;
-            *(u32x4 *)(buf + kTile * kNopeStride + key * kRopeStride + (((r & 7) ^ (key & 7)) * 16)) = st.v[j];
-        }
-    }
+    if (idx < 16) issue_nope_row(nope, wave + 4 * idx, buf, lane);
+    else issue_rope_block(p, rope, buf, wave + 4 * (idx - 16), lane);
 }
 
 template <bool BF16>
-__global__ __launch_bounds__(64 * kMaxWaves) __attribute__((amdgpu_waves_per_eu(kDSplit, kDSplit))) void mla_decode_kernel(MlaParams p)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void mla_decode_kernel(MlaParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, c16 = lane & 15;
     // 1-D grid decode: the head blocks of one (batch, kv head, split) unit sit on one XCD, back to back in dispatch order
     const int head_blocks = (p.group + kHeadsPerBlock - 1) / kHeadsPerBlock;
@@ -217,8 +98,7 @@ __global__ __launch_bounds__(64 * kMaxWaves) __attribute__((amdgpu_waves_per_eu(
         t_begin = split * tps;
         t_end = min(ntiles, t_begin + tps);
     }
-    const int dhalf = wave / kHeadWaves;                         // which slice of the 512 output dims this wave accumulates
-    const int hg = hblk * kHeadsPerBlock + (wave % kHeadWaves) * 16 + c16;      // head inside the kv group
+    const int hg = hblk * kHeadsPerBlock + wave * 16 + c16;      // head inside the kv group
     const bool head_ok = hg < p.group;
     const int head = kvh * p.group + hg;
 
@@ -232,86 +112,44 @@ __global__ __launch_bounds__(64 * kMaxWaves) __attribute__((amdgpu_waves_per_eu(
             else qf[ks] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
         }
     }
-    f32x4 acc[kAccTiles];
+    f32x4 acc[32];
 #pragma unroll
-    for (int i = 0; i < kAccTiles; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 32; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;
 
     TileRowsRaw raw_next = tile_rows_load(p, b, seq_len, t_begin, lane);
-    TileRows rows_nxt{0, 0};
-    StageRegs st, st2;
     if (t_begin < t_end) {
-        if (MLA_STAGE) {
-            const TileRows r0 = tile_rows_finish(p, kvh, raw_next);
-            stage_load(p, r0, 0, wave, lane, st);
-            stage_store(lds, 0, wave, lane, st);
-            stage_load(p, r0, 1, wave, lane, st);
-            stage_store(lds, 1, wave, lane, st);
-        } else {
-            issue_tile(p, tile_rows_finish(p, kvh, raw_next), lds, wave, nwaves, lane);
-        }
+        const TileRows r0 = tile_rows_finish(p, kvh, raw_next);
+        const int64_t a0 = nope_addr(p, r0);
+        // The 18 pieces of the first tile, idx = 0..17, as two ROLLED loops (one per kind).  Unrolled, or as one loop over both kinds, the
+        // prologue costs scalar registers that the allocator then takes from the tile loop: 34-35 SGPR spills instead of 20, with 16 kernel
+        // arguments reloaded by v_readlane in every tile (profiles/latent_tile_engine_refactor.md).
+#pragma nounroll
+        for (int idx = 0; idx < 16; ++idx) issue_piece(p, a0, r0.rope, lds, wave, lane, idx);
+#pragma nounroll
+        for (int idx = 16; idx < 18; ++idx) issue_piece(p, a0, r0.rope, lds, wave, lane, idx);
         raw_next = tile_rows_load(p, b, seq_len, t_begin + 1, lane);
     }
+    const float cs = p.sm_scale * 1.4426950408889634f;
     for (int t = t_begin; t < t_end; ++t) {
         uint8_t *buf = lds + ((t - t_begin) & 1) * kBufBytes;
         uint8_t *nbuf = lds + ((t + 1 - t_begin) & 1) * kBufBytes;
-        const bool more = t + 1 < t_end;
-        if (!MLA_STAGE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's DMA pieces of tile t have landed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's DMA pieces of tile t have landed
         __syncthreads();                                      // tile t is complete in LDS, tile t-1 is no longer read
-        if (MLA_STAGE) {
-            if (more) {
-                rows_nxt = tile_rows_finish(p, kvh, raw_next);
-                stage_load(p, rows_nxt, 0, wave, lane, st);   // first half of tile t+1 travels under the QK MFMAs
-                raw_next = tile_rows_load(p, b, seq_len, t + 2, lane);
-            }
-        } else if (kDmaInterleaved) {
-            rows_nxt = tile_rows_finish(p, kvh, raw_next);     // past the last tile the rows are clamped: a harmless dummy fill
-        } else if (more) {
-            issue_tile(p, tile_rows_finish(p, kvh, raw_next), nbuf, wave, nwaves, lane);
-            raw_next = tile_rows_load(p, b, seq_len, t + 2, lane);      // consumed one iteration later, after the wait above
-        }
+        const TileRows rows_nxt = tile_rows_finish(p, kvh, raw_next);      // past the last tile the rows are clamped: a harmless dummy fill
+        const int64_t nope_nxt = nope_addr(p, rows_nxt);
 
-        // ---- S^T[key, head] = K · Q^T  (4 m-tiles of 16 keys, 18 k-steps of 32 dims)
+        // ---- S^T[key, head] = K · Q^T over 16 nope + 2 rope k-steps; tile t+1 trickles in under the MFMAs
         f32x4 s[4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) s[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
         auto lda = [&](int ks, int mt) -> s16x8 {
-            if (ks < 16) return *(const s16x8 *)(buf + (mt * 16 + c16) * kNopeStride + ks * 64 + g * 16);
+            if (ks < 16) return lda_nope(buf, ks, mt, g, c16);
             const int key = mt * 16 + c16;
             const int chunk = ((ks - 16) * 4 + g) ^ (key & 7);
             return *(const s16x8 *)(buf + kTile * kNopeStride + key * kRopeStride + chunk * 16);
         };
-        // Explicit software pipeline, fenced with sched_barrier so the machine scheduler cannot sink the prefetch back
-        // next to its use: operands of k-step ks + kAhead are issued before the MFMAs of k-step ks.
-        constexpr int kAhead = MLA_QK_AHEAD;
-        s16x8 af[kAhead + 1][4];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int pre = 0; pre < kAhead; ++pre)
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) af[pre][mt] = lda(pre, mt);
-#pragma unroll
-        for (int ks = 0; ks < 18; ++ks) {
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks + kAhead < 18) {
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) af[(ks + kAhead) % (kAhead + 1)][mt] = lda(ks + kAhead, mt);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) s[mt] = mfma16<BF16>(af[ks % (kAhead + 1)][mt], qf[ks], s[mt]);
-            if (kDmaInterleaved) issue_piece(p, rows_nxt, nbuf, wave, lane, ks);    // tile t+1 trickles in under the MFMAs
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (kDmaInterleaved) raw_next = tile_rows_load(p, b, seq_len, t + 2, lane);
-        if (MLA_STAGE && more) {
-            stage_load(p, rows_nxt, 1, wave, lane, st2);      // second half travels under softmax + PV
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // ---- online softmax; lane owns head c16 and keys mt*16 + 4g + r.  Scores stay unscaled: with
-        // c = sm_scale * log2(e), P = exp2(S*c - m*c) is one FMA + one v_exp_f32 per element; m_run / tmax are kept in
-        // the scaled log2 domain.  Only the tile that crosses seq_len needs the key mask.
-        const float cs = p.sm_scale * 1.4426950408889634f;
+        qk_scores<BF16, 18>(lda, qf, s, [&](int ks) { issue_piece(p, nope_nxt, rows_nxt.rope, nbuf, wave, lane, ks); });
+        raw_next = tile_rows_load(p, b, seq_len, t + 2, lane);
+        // ---- only the tile that crosses seq_len needs the key mask; lane owns keys mt*16 + 4g + r
         if ((t + 1) * kTile > seq_len) {
             const int kbase = t * kTile + 4 * g;
 #pragma unroll
@@ -320,102 +158,18 @@ __global__ __launch_bounds__(64 * kMaxWaves) __attribute__((amdgpu_waves_per_eu(
                 for (int r = 0; r < 4; ++r)
                     if (kbase + mt * 16 + r >= seq_len) s[mt][r] = -INFINITY;
         }
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) tmax = fmaxf(fmaxf(tmax, fmaxf(s[mt][0], s[mt][1])), fmaxf(s[mt][2], s[mt][3]));
-        tmax = max_over_rows(tmax);
-        tmax *= cs;                                     // sm_scale > 0: max commutes with the scaling
-        // Deferred rescale: the running reference m_run only moves when some head's tile maximum exceeds it by more
-        // than kDefer (then every head of the wave re-bases to its true maximum); otherwise P = exp2(.) <= 2^kDefer
-        // and neither l nor the 128 accumulators need touching.  out = acc / l is invariant to the reference.
-        constexpr float kDefer = 11.0f;                 // log2 domain (e^8 ~ 2^11.5)
-        if (__any(tmax > m_run + kDefer)) {
-            const float m_new = fmaxf(m_run, tmax);
-            const float alpha = (m_new == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f(m_run - m_new);   // m_run = -inf -> 0
-            l_run *= alpha;
-            m_run = m_new;
-#pragma unroll
-            for (int c = 0; c < kAccTiles / 8; ++c) {           // 8 accumulators at a time keeps the VGPR<->AGPR staging small
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc[c * 8 + i] *= alpha;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        const float nm = (m_run == -INFINITY) ? 0.f : -m_run;
-        float psum = 0.f;
-        uint32_t pk[8];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            float e[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                e[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[mt][r], cs, nm));
-                psum += e[r];
-            }
-            pk[mt * 2 + 0] = pack2<BF16>(e[0], e[1]);
-            pk[mt * 2 + 1] = pack2<BF16>(e[2], e[3]);
-        }
-        psum = sum_over_rows(psum);
-        l_run += psum;
-        if (MLA_STAGE && more) {
-            __builtin_amdgcn_sched_barrier(0);
-            stage_store(nbuf, 0, wave, lane, st);             // first half had QK + softmax to arrive
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // P^T fragments: k-step kk covers key tiles (2kk, 2kk+1); slots 0..3 / 4..7 of lane group g
         s16x8 pf[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const u32x4 w = u32x4{pk[kk * 4 + 0], pk[kk * 4 + 1], pk[kk * 4 + 2], pk[kk * 4 + 3]};
-            pf[kk] = __builtin_bit_cast(s16x8, w);
-        }
-        // ---- O^T[d, head] += V^T · P^T   (V = nope part of the same LDS tile, transposed on the fly)
-        const uint8_t *vrow = buf + (4 * g + (c16 >> 2)) * kNopeStride + (c16 & 3) * 8 + dhalf * kAccTiles * 32;
-        auto ldv = [&](int i, int half) -> s16x4 {      // i = kk * kAccTiles + dt
-            const int kk = i / kAccTiles, dt = i % kAccTiles;
-            return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (s16x4 __attribute__((address_space(3))) *)(vrow + (2 * kk + half) * 16 * kNopeStride + dt * 32));
-        };
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 2 * kAccTiles; ++i) {
-            const s16x4 lo = ldv(i, 0), hi = ldv(i, 1);
-            const s16x8 a = s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            acc[i % kAccTiles] = mfma16<BF16>(a, pf[i / kAccTiles], acc[i % kAccTiles]);
-        }
-        constexpr int kPvAhead = kDSplit == 1 ? 8 : 6;          // MFMAs' worth of tr-reads in flight (<= 15 DS ops)
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * kPvAhead, 0);
-#pragma unroll
-        for (int i = 0; i < 2 * kAccTiles - kPvAhead; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, kPvAhead, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (MLA_STAGE && more) stage_store(nbuf, 1, wave, lane, st2);
+        softmax_step<BF16, false>(s, cs, m_run, l_run, acc, pf);
+        pv_accumulate<BF16>(buf, pf, acc, g, c16);
     }
 
-    if (kDmaInterleaved) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the dummy fill issued under the last tile
-    // ---- epilogue: lane holds O^T[d = dt*16 + 4g + r][head c16]
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the dummy fill issued under the last tile
     if (!head_ok) return;
     if (nsp == 1) {
-        const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-        uint16_t *orow = p.out + (int64_t)b * p.o_sb + (int64_t)head * p.o_sh + 4 * g + dhalf * kAccTiles * 16;
-#pragma unroll
-        for (int dt = 0; dt < kAccTiles; ++dt) {
-            const uint32_t w0 = (uint32_t)cvt_out<BF16>(acc[dt][0] * inv) | ((uint32_t)cvt_out<BF16>(acc[dt][1] * inv) << 16);
-            const uint32_t w1 = (uint32_t)cvt_out<BF16>(acc[dt][2] * inv) | ((uint32_t)cvt_out<BF16>(acc[dt][3] * inv) << 16);
-            *(uint2 *)(orow + dt * 16) = uint2{w0, w1};
-        }
+        store_head_out<BF16>(p.out + (int64_t)b * p.o_sb + (int64_t)head * p.o_sh, acc, l_run, g);
     } else {
         const int64_t idx = p.plan ? (int64_t)blockIdx.x * p.group + hg : ((int64_t)b * p.q_heads + head) * p.num_splits + split;
-        float *po = p.ws_o + idx * kDN + 4 * g + dhalf * kAccTiles * 16;
-#pragma unroll
-        for (int dt = 0; dt < kAccTiles; ++dt) *(f32x4 *)(po + dt * 16) = acc[dt];
-        if (g == 0 && dhalf == 0) {
-            p.ws_ml[idx * 2 + 0] = m_run;
-            p.ws_ml[idx * 2 + 1] = l_run;
-        }
+        store_head_partial(p.ws_o + idx * kDN, p.ws_ml + idx * 2, acc, m_run, l_run, g);
     }
 }
 
@@ -532,18 +286,6 @@ static size_t partial_bytes(int batch, int q_heads, int num_splits)
     return num_splits <= 1 ? 0 : (size_t)batch * q_heads * num_splits * (kDN + 2) * sizeof(float);
 }
 
-// workgroups the chip runs at once with one wide workgroup per CU (the plan's `workers`); 256 when no device answers
-static int plan_workers()
-{
-    static int cached[64];
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 256;
-    if (!cached[d]) {
-        int n = 0;
-        cached[d] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0) ? n : 256;
-    }
-    return cached[d];
-}
 // planned form: one partial row per (item, head of its kv group).  kv_heads is not an argument of the workspace query; for any kv_heads
 // the rows are items * group <= (seqs + workers + pad) * group = batch * q_heads + (workers + pad) * group, and the planned form serves
 // groups of <= 128 heads; the list itself is sized for the most (sequence, kv head) pairs the query allows, batch * q_heads
@@ -559,7 +301,7 @@ extern "C" size_t mi_mla_decode_workspace(int batch, int q_heads, int num_splits
     if (batch <= 0 || q_heads <= 0) return 0;
     if (num_splits == MI_MLA_SPLITS_PLANNED) {
         const long long seqs = planned_seqs_bound(batch, q_heads);
-        const int workers = plan_workers();
+        const int workers = mi_gqa::cus();      // the plan's `workers`: workgroups the chip runs at once with one per CU
         return planned_partial_bytes(batch, q_heads, workers) + (size_t)batch * q_heads * sizeof(uint32_t) + plan_words(seqs, workers) * sizeof(int32_t);
     }
     return partial_bytes(batch, q_heads, num_splits) + (size_t)batch * q_heads * sizeof(uint32_t);   // q_heads >= kv_heads
@@ -570,16 +312,16 @@ static bool use_wide(int group)
     // MI_MLA_WIDE=0: groups of more than 64 heads also run the 64-head kernel, as ceil(group / 64) sibling workgroups per sequence that
     // share an XCD (A/B switch; DESIGN section 4.1 has the measurement)
     static const bool allow = !(getenv("MI_MLA_WIDE") && atoi(getenv("MI_MLA_WIDE")) == 0);
-    return allow && group > kHeadsPerBlock && MLA_WAVES == 4;
+    return allow && group > kHeadsPerBlock;
 }
 
 // introspection for tests and tuning: where the work list sits in a planned workspace, and the worker count it was built for
 extern "C" size_t mi_mla_decode_plan_offset(int batch, int q_heads)
 {
     if (batch <= 0 || q_heads <= 0) return 0;
-    return planned_partial_bytes(batch, q_heads, plan_workers()) + (size_t)batch * q_heads * sizeof(uint32_t);
+    return planned_partial_bytes(batch, q_heads, mi_gqa::cus()) + (size_t)batch * q_heads * sizeof(uint32_t);
 }
-extern "C" int mi_mla_decode_plan_workers(void) { return plan_workers(); }
+extern "C" int mi_mla_decode_plan_workers(void) { return mi_gqa::cus(); }
 
 static int g_wide_variant = 0;      // 0 = environment / default; 4, 8 or 9 = forced (tests run every form in one process)
 static int wide_variant()
@@ -648,12 +390,12 @@ extern "C" int mi_mla_decode_select_wide(int waves)
 extern "C" size_t mi_mla_decode_plan_bytes(int batch, int kv_heads)
 {
     if (batch <= 0 || kv_heads <= 0) return 0;
-    return plan_words((long long)batch * kv_heads, plan_workers()) * sizeof(int32_t);
+    return plan_words((long long)batch * kv_heads, mi_gqa::cus()) * sizeof(int32_t);
 }
 extern "C" int mi_mla_decode_build_plan(const int32_t *kv_seq_lens, int batch, int kv_heads, void *plan, size_t plan_bytes, void *stream)
 {
     if (batch <= 0 || kv_heads <= 0 || !kv_seq_lens || !plan || plan_bytes < mi_mla_decode_plan_bytes(batch, kv_heads)) return MI_SGL_EINVAL;
-    decode_plan_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(kv_seq_lens, batch, kv_heads, kWideTile, kTile / kWideTile, plan_workers(), (int32_t *)plan);
+    decode_plan_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(kv_seq_lens, batch, kv_heads, kWideTile, kTile / kWideTile, mi_gqa::cus(), (int32_t *)plan);
     return hipGetLastError() == hipSuccess ? MI_SGL_OK : MI_SGL_ELAUNCH;
 }
 
@@ -702,8 +444,8 @@ static int mla_decode_impl(const void *q, const void *k_nope, const void *k_rope
     if (batch == 0) return MI_SGL_OK;
     if (!q || !k_nope || !k_rope || !out || !kv_seq_lens || !block_table) return MI_SGL_EINVAL;
     if (dtype != MI_DTYPE_BF16 && dtype != MI_DTYPE_F16) return MI_SGL_EINVAL;
-    if ((q_stride_h % 8) || (q_stride_b % 8) || (kn_stride_row % 8) || (kn_stride_blk % 8) || (kn_stride_h % 8) ||
-        (kr_stride_row % 8) || (kr_stride_blk % 8) || (kr_stride_h % 8) || (o_stride_h % 8) || (o_stride_b % 8))
+    if (!mi_gqa::aligned8({q_stride_h, q_stride_b, kn_stride_row, kn_stride_blk, kn_stride_h, kr_stride_row, kr_stride_blk, kr_stride_h, o_stride_h,
+                           o_stride_b}))
         return MI_SGL_EINVAL;      // 16-byte vector accesses
     if (num_splits == 0) num_splits = mi_mla_decode_num_splits(batch, q_heads, kv_heads, max_seq_len);
     if (num_splits < 0 && num_splits != MI_MLA_SPLITS_PLANNED) return MI_SGL_EINVAL;
@@ -731,7 +473,7 @@ static int mla_decode_impl(const void *q, const void *k_nope, const void *k_rope
     MlaParams p;
     p.plan = nullptr;
     const long long seqs = (long long)batch * kv_heads;
-    const int workers = plan_workers();
+    const int workers = mi_gqa::cus();
     p.q = (const uint16_t *)q, p.k_nope = (const uint16_t *)k_nope, p.k_rope = (const uint16_t *)k_rope;
     p.out = (uint16_t *)out, p.seq_lens = kv_seq_lens, p.block_table = block_table;
     p.ws_o = (float *)workspace;
@@ -792,11 +534,10 @@ static int mla_decode_impl(const void *q, const void *k_nope, const void *k_rope
         p.fix_only = 1;                                // the merge kernel also serves as the slow path for flagged sequences
     } else {
         const int head_blocks = (p.group + kHeadsPerBlock - 1) / kHeadsPerBlock;
-        const int nwaves = kHeadWaves * kDSplit;      // head waves beyond the group size only help with the DMA
         dim3 grid((unsigned)(planned ? plan_items_max(seqs, workers) : ((units + 7) / 8) * 8 * head_blocks));
         const size_t lds = 2 * (size_t)kBufBytes;
-        if (dtype == MI_DTYPE_BF16) mla_decode_kernel<true><<<grid, 64 * nwaves, lds, st>>>(p);
-        else mla_decode_kernel<false><<<grid, 64 * nwaves, lds, st>>>(p);
+        if (dtype == MI_DTYPE_BF16) mla_decode_kernel<true><<<grid, 256, lds, st>>>(p);      // head waves beyond the group size only help with the DMA
+        else mla_decode_kernel<false><<<grid, 256, lds, st>>>(p);
     }
     if ((num_splits > 1 || wide || planned) && !p.inline_merge) {
         const long long bh = (long long)batch * q_heads;

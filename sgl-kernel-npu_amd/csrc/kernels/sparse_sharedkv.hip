@@ -4,20 +4,23 @@
 // Replaces the reference's AscendC op csrc/sparse_attn_sharedkv/ (op_kernel/arch32/sparse_attn_sharedkv_{swa,scfa}_kernel.h); the semantics
 // are stated in include/mi_sgl_kernels.h and DESIGN.md 4.3.6.
 //
-// Schedule: the 64-heads-per-workgroup form of mla_decode.hip without the rope part.
+// Schedule: the 64-heads-per-workgroup form of mla_decode.hip without the rope part; the tile engine both share (fill primitive, QK pipeline,
+// softmax step, P.V, the two finishes) is latent_tile_dev.h.  This file holds the op's own: the key list and its three-step addressing, the
+// mask from the tile's ballot, the tile skip, the sink start values and the merge.
 //  * one workgroup = one query token x one piece of its key list; 4 waves, one per SIMD, 16 heads each (lane = head for the softmax
 //    statistics), all 512 output dims per wave (128 accumulators + 64 resident Q^T registers);
 //  * the key list of a token is its window keys followed by its index slots (or by the `limit` compressed keys).  Lane l of a tile owns list
 //    position 64 t + l and turns it into the absolute address of one 1-KiB row: window position -> ori_block_table -> ori_kv, slot -> index
 //    -> cmp_block_table -> cmp_kv (64-bit offsets), in three steps that run one tile apart (index of tile t + 3, table entry of tile t + 2,
 //    address + fill of tile t + 1 under the MFMAs of tile t) so no load is waited for where it is issued;
-//  * tiles of 64 rows go global -> LDS by LDS-DMA (global_load_lds_dwordx4, one row per wave-instruction, issued one per QK k-step: 16 rows
-//    per wave = 16 k-steps), double buffered (2 x 66 KB), one barrier per tile; rows padded to 1056 B as in mla_decode.hip;
+//  * tiles of 64 rows go global -> LDS by LDS-DMA (one row per wave-instruction, issued one per QK k-step: 16 rows per wave = 16 k-steps),
+//    double buffered (2 x 66 KB), one barrier per tile; rows padded to 1056 B as in mla_decode.hip;
 //  * a position that does not count (slot < 0 or >= limit, or behind the list) is masked to -inf in S and its row address is the token's own
 //    newest window key: the caches may hold anything (NaN) in rows the token must not read, and 0 * NaN would reach O through P.V.  A tile
 //    without a counting position is neither filled nor computed (wave-uniform test on the tile's ballot), wherever it stands;
-//  * online softmax as in mla_decode.hip (scaled log2 domain, deferred rescale) with the running reference kept a whole number; piece 0
-//    starts from the sink, (m, l) = (ceil(sink), 2^(sink - m)) -- the (sink, 1) of the semantics --, the others from (-inf, 0); with one piece the kernel writes the output, otherwise a merge kernel combines the fp32 (m, l, O) partials.
+//  * online softmax in the engine's whole-number-reference form (softmax_step<., true>); piece 0 starts from the sink, (m, l) = (ceil(sink),
+//    2^(sink - m)) -- the (sink, 1) of the semantics --, the others from (-inf, 0); with one piece the kernel writes the output, otherwise a
+//    merge kernel combines the fp32 (m, l, O) partials.
 // Algorithmic HBM bytes per call: sum over tokens of (counting keys) * 1024 + tokens * 64 * 512 * 2 * 2 (Q, out).
 #include "device_once.h"
 #include <hip/hip_runtime.h>
@@ -26,7 +29,7 @@
 
 #include "mi_sgl_kernels.h"
 #include "gqa_common.h"      // cus()
-#include "mla_common.h"
+#include "latent_tile_dev.h"
 
 namespace mi_sgl {
 namespace {
@@ -49,32 +52,6 @@ struct SskParams {
     int64_t ori_sblk, cmp_sblk, ori_bt_sb, cmp_bt_sb;      // rows of a page are contiguous (512 elements apart)
     float sm_scale;
 };
-
-__device__ __forceinline__ float row_max(float x)
-{
-    typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-    const unsigned u = __float_as_uint(x);
-    const u32x2v a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const unsigned v = __float_as_uint(fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1])));
-    const u32x2v b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float row_sum(float x)
-{
-    typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-    const unsigned u = __float_as_uint(x);
-    const u32x2v a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const unsigned v = __float_as_uint(__uint_as_float(a[0]) + __uint_as_float(a[1]));
-    const u32x2v b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
-// LDS-DMA of one 1-KiB row (mla_decode.hip has the reasoning for the inline asm): lane l moves 16 B from its own address to dst + 16 l
-__device__ __forceinline__ void dma_row(const uint8_t *dst_lds, const void *vaddr)
-{
-    const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)dst_lds);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(dst), "v"(vaddr) : "memory");
-}
 
 // What a token attends to, the same in every lane of its workgroup.
 struct Token {
@@ -133,16 +110,6 @@ __device__ __forceinline__ Rows pick_rows(const SskParams &p, const Token &tk, c
     r.counts = __ballot(k.kind != 0);
     return r;
 }
-// row wave + 4 idx of the tile, one of the 16 DMA instructions a wave contributes (spread over its QK k-steps)
-__device__ __forceinline__ void issue_row(const Rows &rows, uint8_t *buf, int wave, int lane, int idx)
-{
-    const int i = wave + 4 * idx;
-    const int lo = __builtin_amdgcn_readlane((int)(rows.addr & 0xFFFFFFFFll), i);
-    const int hi = __builtin_amdgcn_readlane((int)(rows.addr >> 32), i);
-    const uint8_t *src = (const uint8_t *)(uintptr_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-    dma_row(buf + i * kNopeStride, src + lane * 16);
-}
-
 template <bool BF16>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void sparse_sharedkv_kernel(SskParams p)
 {
@@ -221,10 +188,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
     for (int j = 0; j < 32; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     // scaled log2 domain; the sink is a virtual key of logit sinks[h] (not multiplied by the scale) and value 0, owned by piece 0.  The
-    // running reference m_run is kept a WHOLE number: P = exp2(x - m_run) then differs between two references by a power of two, which the
-    // rounding of P to the KV dtype commutes with -- the rounded P does not depend on the tile order, the split count or the sink the
-    // reference starts from, and the partials of the pieces merge with exact weights.  (Against the running maximum itself a row of three
-    // keys missed the tests' tolerance: each P's rounding error is relative to its term, the terms cancel.)
+    // running reference starts a whole number and stays one (softmax_step<., true> has the reason).
     const float sink_l2 = p.sinks[head] * 1.4426950408889634f;
     float m_run = split == 0 ? ceilf(sink_l2) : -INFINITY;
     float l_run = split == 0 ? __builtin_amdgcn_exp2f(sink_l2 - m_run) : 0.f;
@@ -237,7 +201,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     bl_b = pick_block(p, tk, pk_a);
     pk_a = pick_key(p, tk, t_begin + 2, t_end, lane);
     if (rows_cur.counts)
-        for (int r = 0; r < 16; ++r) issue_row(rows_cur, lds, wave, lane, r);
+        for (int r = 0; r < 16; ++r) issue_nope_row(rows_cur.addr, wave + 4 * r, lds, lane);
 
     const float cs = p.sm_scale * 1.4426950408889634f;
     for (int t = t_begin; t < t_end; ++t) {
@@ -256,36 +220,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // a tile that does not count computes nothing, so the fill of its successor is issued here at once.  (One fill site in front of the
         // branch, not inside the skipped arm: with the DMA statements in that arm the allocator spilled 138 registers per lane.)
         if (fill && counts == 0)
-            for (int r = 0; r < 16; ++r) issue_row(rows_nxt, nbuf, wave, lane, r);
+            for (int r = 0; r < 16; ++r) issue_nope_row(rows_nxt.addr, wave + 4 * r, nbuf, lane);
         if (counts == 0) continue;                            // nothing of this tile counts: it was not filled and is not computed
 
-        // ---- S^T[key, head] = K . Q^T  (4 m-tiles of 16 keys, 16 k-steps of 32 dims), operands three k-steps ahead
+        // ---- S^T[key, head] = K . Q^T over 16 k-steps; tile t + 1 trickles in under the MFMAs
         f32x4 s[4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) s[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        auto lda = [&](int ks, int mt) -> s16x8 { return *(const s16x8 *)(buf + (mt * 16 + c16) * kNopeStride + ks * 64 + g * 16); };
-        constexpr int kAhead = 3;
-        s16x8 af[kAhead + 1][4];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int pre = 0; pre < kAhead; ++pre)
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) af[pre][mt] = lda(pre, mt);
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) {
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks + kAhead < 16) {
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) af[(ks + kAhead) % (kAhead + 1)][mt] = lda(ks + kAhead, mt);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) s[mt] = mfma16<BF16>(af[ks % (kAhead + 1)][mt], qf[ks], s[mt]);
-            if (fill) issue_row(rows_nxt, nbuf, wave, lane, ks);      // tile t + 1 trickles in under the MFMAs
-        }
-        __builtin_amdgcn_sched_barrier(0);
-
-        // ---- online softmax; lane owns head c16 and keys mt*16 + 4g + r.  P = exp2(S*c - m*c) with c = sm_scale * log2(e)
+        qk_scores<BF16, 16>([&](int ks, int mt) { return lda_nope(buf, ks, mt, g, c16); }, qf, s, [&](int ks) {
+            if (fill) issue_nope_row(rows_nxt.addr, wave + 4 * ks, nbuf, lane);
+        });
+        // ---- lane owns keys mt*16 + 4g + r: the positions that do not count are masked
         if (~counts) {
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt)
@@ -293,87 +236,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 for (int r = 0; r < 4; ++r)
                     if (!((counts >> (mt * 16 + 4 * g + r)) & 1ull)) s[mt][r] = -INFINITY;
         }
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) tmax = fmaxf(fmaxf(tmax, fmaxf(s[mt][0], s[mt][1])), fmaxf(s[mt][2], s[mt][3]));
-        tmax = row_max(tmax);
-        tmax = tmax == -INFINITY ? tmax : tmax * cs;          // sm_scale >= 0: max commutes with the scaling (and -inf * 0 is kept out)
-        constexpr float kDefer = 11.0f;                       // deferred rescale, as in mla_decode.hip
-        if (__any(tmax > m_run + kDefer)) {
-            const float m_new = ceilf(fmaxf(m_run, tmax));
-            const float alpha = (m_new == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f(m_run - m_new);
-            l_run *= alpha;
-            m_run = m_new;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[c * 8 + j] *= alpha;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        const float nm = (m_run == -INFINITY) ? 0.f : -m_run;
-        float psum = 0.f;
-        uint32_t pk[8];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            float e[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                e[r] = s[mt][r] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(__builtin_fmaf(s[mt][r], cs, nm));
-                psum += e[r];
-            }
-            pk[mt * 2 + 0] = pack2<BF16>(e[0], e[1]);
-            pk[mt * 2 + 1] = pack2<BF16>(e[2], e[3]);
-        }
-        psum = row_sum(psum);
-        l_run += psum;
         s16x8 pf[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) pf[kk] = __builtin_bit_cast(s16x8, u32x4{pk[kk * 4 + 0], pk[kk * 4 + 1], pk[kk * 4 + 2], pk[kk * 4 + 3]});
-        // ---- O^T[d, head] += V^T . P^T   (V = the same LDS tile, transposed on the fly)
-        const uint8_t *vrow = buf + (4 * g + (c16 >> 2)) * kNopeStride + (c16 & 3) * 8;
-        auto ldv = [&](int j, int half) -> s16x4 {      // j = kk * 32 + dt
-            const int kk = j / 32, dt = j % 32;
-            return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (s16x4 __attribute__((address_space(3))) *)(vrow + (2 * kk + half) * 16 * kNopeStride + dt * 32));
-        };
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 64; ++j) {
-            const s16x4 lo = ldv(j, 0), hi = ldv(j, 1);
-            const s16x8 a = s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            acc[j % 32] = mfma16<BF16>(a, pf[j / 32], acc[j % 32]);
-        }
-        constexpr int kPvAhead = 8;
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * kPvAhead, 0);
-#pragma unroll
-        for (int j = 0; j < 64 - kPvAhead; ++j) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, kPvAhead, 0);
-        __builtin_amdgcn_sched_barrier(0);
+        softmax_step<BF16, true>(s, cs, m_run, l_run, acc, pf);
+        pv_accumulate<BF16>(buf, pf, acc, g, c16);
     }
 
-    // ---- epilogue: lane holds O^T[d = dt*16 + 4g + r][head c16]
-    if (nsp == 1) {
-        const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-        uint16_t *orow = p.out + o_off + (int64_t)head * p.o_sh + 4 * g;
-#pragma unroll
-        for (int dt = 0; dt < 32; ++dt) {
-            const uint32_t w0 = (uint32_t)cvt_out<BF16>(acc[dt][0] * inv) | ((uint32_t)cvt_out<BF16>(acc[dt][1] * inv) << 16);
-            const uint32_t w1 = (uint32_t)cvt_out<BF16>(acc[dt][2] * inv) | ((uint32_t)cvt_out<BF16>(acc[dt][3] * inv) << 16);
-            *(uint2 *)(orow + dt * 16) = uint2{w0, w1};
-        }
-    } else {
-        float *po = p.ws_o + slot * kDN + 4 * g;
-#pragma unroll
-        for (int dt = 0; dt < 32; ++dt) *(f32x4 *)(po + dt * 16) = acc[dt];
-        if (g == 0) {
-            p.ws_ml[slot * 2 + 0] = m_run;
-            p.ws_ml[slot * 2 + 1] = l_run;
-        }
-    }
+    if (nsp == 1) store_head_out<BF16>(p.out + o_off + (int64_t)head * p.o_sh, acc, l_run, g);
+    else store_head_partial(p.ws_o + slot * kDN, p.ws_ml + slot * 2, acc, m_run, l_run, g);
 }
 
 // merge the partials of a token's pieces: one wave per (token, head), lane handles 8 of the 512 dims.  Piece 0 carries the sink in its
