@@ -224,7 +224,10 @@ extern "C" size_t mi_ep_dispatch_layout_workspace(int T, int K, int E)
     (void)K;
     size_t U = (size_t)(T + kUnitTokens - 1) / kUnitTokens;
     if (U == 0) U = 1;
-    return U * (2 * (size_t)E + MI_EP_MAX_RANKS) * sizeof(int32_t);
+    // three launches: [U][E] histograms, [U][E] bases, [U][W] rank counts.  The cooperative launch needs one row of
+    // layout_row_words(E, W) words per workgroup of at least 256 tokens: never more than the above, the maximum states it.
+    const size_t three = U * (2 * (size_t)E + MI_EP_MAX_RANKS), coop = ((size_t)T + 255) / 256 * (size_t)layout_row_words(E, MI_EP_MAX_RANKS);
+    return (three > coop ? three : coop) * sizeof(int32_t);
 }
 
 extern "C" int mi_ep_dispatch_layout(const void *topk_idx, int idx_is_i32, int T, int K, int E, int W,
@@ -262,9 +265,11 @@ extern "C" int mi_ep_dispatch_layout(const void *topk_idx, int idx_is_i32, int T
     const int Us = (T + ut - 1) / ut;
     const int Bc = (Us + 15) / 16;                         // workgroups of 16 units
     const bool single = Us >= 1 && Us <= 16;
-    const bool coop = Us > 16 && lend && Bc <= 128 && workspace_bytes >= (size_t)Bc * (E + MI_EP_MAX_RANKS) * sizeof(int32_t);
+    // (rows of whole 128-byte lines: the totals are handed over write-through, layout_dev.h)
+    const bool coop = Us > 16 && lend && Bc <= 128 && workspace_bytes >= (size_t)Bc * layout_row_words(E, W) * sizeof(int32_t) &&
+                      ((uintptr_t)workspace & 127) == 0;
     if ((single || coop) && (size_t)16 * E <= 16384 && ((16 * E) & 1) == 0) {
-        const size_t ldsf = layout_small_lds_bytes(E, W, ut);
+        const size_t ldsf = coop ? layout_coop_lds_bytes(E, W, ut) : layout_small_lds_bytes(E, W, ut);
         static PerDeviceOnce attr_once;
         if (attr_once.need()) {
             (void)hipFuncSetAttribute((const void *)layout_small_kernel<true, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
