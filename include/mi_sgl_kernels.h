@@ -14,6 +14,7 @@
  *                               (flash_prefill_bnsd_score, flash_prefill_bnsd_topk_from_score, flash_prefill_bnsd_with_topk_idx)
  *   mi_lightning_indexer     <- csrc/lightning_indexer/ (torch.ops.npu.lightning_indexer)
  *   mi_sparse_attn_sharedkv  <- csrc/sparse_attn_sharedkv/ (torch.ops.npu.sparse_attn_sharedkv)
+ *   mi_compressor            <- csrc/compressor/ (torch.ops.npu.compressor)
  *   mi_swiglu_quant          <- activation/swiglu_quant.py:8-127     (_swiglu_quant_kernel / swiglu_quant)
  *   mi_add_rmsnorm_bias      <- norm/add_rmsnorm_bias.py:8-147        (add_rmsnorm_bias_kernel / add_rmsnorm_bias)
  *                               norm/add_rmsnorm_bias.py:150-232      (add_gemma_rms_norm)
@@ -310,6 +311,51 @@ int mi_sparse_attn_sharedkv(const void *q, const void *ori_kv, const void *cmp_k
                             int64_t o_stride_s, int64_t o_stride_h, int64_t idx_stride_b, int64_t idx_stride_s, int64_t ori_stride_blk,
                             int64_t cmp_stride_blk, int64_t ori_bt_stride, int64_t cmp_bt_stride, float softmax_scale, int cmp_ratio, int ori_win_left, int ori_win_right, int dtype,
                             int num_splits, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- KV compressor (csrc/compressor/: torch.ops.npu.compressor) -------------------------------------------------------------------------
+ * The producer of the compressed cache the two ops above consume.  x: layout MI_COMPRESSOR_TH [tokens, hidden] with cu_seqlens [batch + 1]
+ * from 0, or MI_COMPRESSOR_BSH [batch, seq, hidden] (tokens = batch * seq, cu_seqlens NULL), contiguous, dtype BF16 / F16; wkv, wgate
+ * [ww, hidden] of the same dtype, ww = coff * head_dim = coff * D; ape [cmp_ratio, ww], norm_weight [D], rope_sin / rope_cos [out_rows, 64]
+ * fp32; state_cache [state_blocks, block_size, 2 ww] fp32 contiguous, columns [0, ww) kv and [ww, 2 ww) score, updated in place.
+ * Sequence b holds span_b tokens (cu[b + 1] - cu[b], or seq) of which used_b = seqused[b] clamped to [0, span_b] (NULL: span_b) exist; token
+ * i < used_b stands at position start_pos[b] + i (NULL: zeros), r = cmp_ratio.
+ *   projections   kv = x . wkv^T, score = x . wgate^T + ape[pos % r], fp32;
+ *   state save    cache_mode 1 (paged): row [kv | score] of every token to block state_block_table[b, pos / block_size], offset pos %
+ *                 block_size; a table entry of 0 is never written (it is still read), one outside the cache is skipped.  cache_mode 2
+ *                 (explicit): to flat row state_block_table[b, coff r + i] of the cache viewed as [-1, 2 ww], only for positions of groups
+ *                 that start at or behind ((start + used) / r) r - (coff - 1) r;
+ *   compress      for every group of r positions that ends inside this call (group start < ((start + used) / r) r), in order: stack the
+ *                 group's rows, channels [(coff - 1) D, coff D), behind -- coff = 2 -- the previous group's rows, channels [0, D); a row
+ *                 comes from this call's projections where its position is >= start_pos and from state_cache (through the table of the cache
+ *                 mode) where it is before; before position 0 it is kv 0, score -inf.  Softmax over the stacked rows per channel, weighted
+ *                 sum of kv, RMSNorm over D (norm_weight, norm_eps), RoPE on the last 64 channels (rotary_mode 1: halves (i, i + 32), 2:
+ *                 pairs (2 i, 2 i + 1); element e reads table column e), cast to x's dtype;
+ *   output        TH: cmp_kv [out_rows = min(tokens, tokens / r + batch), D], rows packed in order of (sequence, group), row i with rope row
+ *                 i; BSH: [batch, ceil(seq / r), D], out_rows = batch * ceil(seq / r).  Rows no group fills are written as zeros.
+ * State rows are read by a launch that runs BEFORE the one that writes them, so a table that maps a position this call writes onto the slot
+ * of a position it reads as history (a ring) is served; the table must not map two positions this call WRITES to one slot.
+ * Nothing is read back by the host (capturable in a graph); the results are the same bits from run to run.  workspace: at least
+ * mi_compressor_workspace() bytes (host arithmetic; 256 CUs when no device answers; 0 for arguments mi_compressor refuses).
+ * LIMITS (MI_SGL_EINVAL beyond them, checked before any pointer is touched): (cmp_ratio, coff, head_dim) one of (4, 2, 512), (4, 2, 128),
+ * (128, 1, 512); 1024 <= hidden <= 10240, a multiple of 512; rope_head_dim 64; rotary_mode 1 / 2; cache_mode 1 / 2; table_dims 1 / 2, in
+ * cache_mode 2 it is 2 with table_cols >= coff r + 1; state_cache_stride_dim0 0 or block_size * 2 ww; out_rows as above.
+ * tokens = 0 or batch = 0: MI_SGL_OK without a launch. */
+#define MI_COMPRESSOR_TH 0
+#define MI_COMPRESSOR_BSH 1
+typedef struct mi_compressor_params {
+    const void *x, *wkv, *wgate;
+    float *state_cache;
+    const float *ape, *norm_weight, *rope_sin, *rope_cos;
+    const int32_t *state_block_table, *cu_seqlens, *seqused, *start_pos;      /* seqused, start_pos: NULL allowed */
+    void *cmp_kv;
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t tokens, out_rows, state_blocks, table_stride, state_cache_stride_dim0;
+    int layout, batch, seq, hidden, head_dim, cmp_ratio, coff, rope_head_dim, rotary_mode, cache_mode, block_size, table_dims, table_cols, dtype;
+    float norm_eps;
+} mi_compressor_params;
+size_t mi_compressor_workspace(int64_t tokens, int batch, int hidden, int head_dim, int coff);
+int mi_compressor(const mi_compressor_params *params, void *stream);
 
 /* ---- SwiGLU + per-row INT8 quantisation (swiglu_quant.py:87-127) -------------------------------------------------
  * x [rows, cols] (cols = 2I; gate = x[:, :I], up = x[:, I:]); only the first `total` rows are processed, where total =

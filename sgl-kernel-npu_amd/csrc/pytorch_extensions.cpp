@@ -745,6 +745,101 @@ std::tuple<at::Tensor, at::Tensor> sparse_attn_sharedkv(
     return {attention_out, softmax_lse};
 }
 
+// csrc/compressor/op_host/compressor.cpp:157-305 (checks: op_host/compressor_tiling.h:111-139, :215-225 and compressor_tiling.cpp:808-997):
+// the KV compressor that produces the cache lightning_indexer and sparse_attn_sharedkv read (csrc/kernels/compressor.hip; semantics in
+// include/mi_sgl_kernels.h).  Returns cmp_kv with every row written (rows no group fills are zeros); state_cache is updated in place.
+// seqused = None: every token of a sequence exists; start_pos = None: zeros (GetSeqUsed / GetStartPos of the reference kernel).
+at::Tensor compressor(const at::Tensor &x, const at::Tensor &wkv, const at::Tensor &wgate, at::Tensor &state_cache, const at::Tensor &ape,
+                      const at::Tensor &norm_weight, const at::Tensor &rope_sin, const at::Tensor &rope_cos,
+                      const std::optional<at::Tensor> &state_block_table, const std::optional<at::Tensor> &cu_seqlens,
+                      const std::optional<at::Tensor> &seqused, const std::optional<at::Tensor> &start_pos, int64_t rope_head_dim,
+                      int64_t cmp_ratio, int64_t coff, double norm_eps, int64_t rotary_mode, int64_t cache_mode,
+                      int64_t state_cache_stride_dim0)
+{
+    const c10::DeviceGuard device_guard(x.device());   // launches and the current stream follow the tensor's GPU
+    TORCH_CHECK(x.scalar_type() == at::kHalf || x.scalar_type() == at::kBFloat16, "compressor: Tensor x only supports dtype float16 or bfloat16");
+    TORCH_CHECK(wkv.scalar_type() == x.scalar_type() && wgate.scalar_type() == x.scalar_type(),
+                "compressor: wkv and wgate datatype should be same with x");
+    auto f32 = [](const at::Tensor &t, const char *name) { TORCH_CHECK(t.scalar_type() == at::kFloat, "compressor: Tensor ", name, " only supports dtype float32"); };
+    f32(state_cache, "state_cache"), f32(ape, "ape"), f32(norm_weight, "norm_weight"), f32(rope_sin, "rope_sin"), f32(rope_cos, "rope_cos");
+    auto i32 = [](const std::optional<at::Tensor> &t, const char *name) {
+        TORCH_CHECK(!t.has_value() || t->scalar_type() == at::kInt, "compressor: Tensor ", name, " only supports dtype int32");
+    };
+    i32(state_block_table, "state_block_table"), i32(cu_seqlens, "cu_seqlens"), i32(seqused, "seqused"), i32(start_pos, "start_pos");
+    auto same_device = [&](const at::Tensor &t, const char *name) { TORCH_CHECK(t.device() == x.device(), "compressor: ", name, " must be on the same device as x"); };
+    same_device(wkv, "wkv"), same_device(wgate, "wgate"), same_device(state_cache, "state_cache"), same_device(ape, "ape");
+    same_device(norm_weight, "norm_weight"), same_device(rope_sin, "rope_sin"), same_device(rope_cos, "rope_cos");
+    for (const auto *t : {&state_block_table, &cu_seqlens, &seqused, &start_pos})
+        if (t->has_value()) same_device(**t, "an int32 input");
+    TORCH_CHECK(x.dim() == 2 || x.dim() == 3, "compressor: x dim number only supports 2 (TH) or 3 (BSH)");
+    const bool th = x.dim() == 2;
+    TORCH_CHECK(wkv.dim() == 2 && wgate.dim() == 2 && state_cache.dim() == 3 && ape.dim() == 2 && norm_weight.dim() == 1,
+                "compressor: wkv, wgate and ape must be 2-dimensional, state_cache 3-dimensional, norm_weight 1-dimensional");
+    TORCH_CHECK(rope_sin.dim() == x.dim() && rope_cos.dim() == x.dim(), "compressor: rope_sin / rope_cos dim num should be equal to x");
+    TORCH_CHECK(state_block_table.has_value(), "compressor: tensor state_block_table is required");
+    TORCH_CHECK(state_block_table->dim() == 1 || state_block_table->dim() == 2, "compressor: state_block_table must be 1- or 2-dimensional");
+    TORCH_CHECK(!th || cu_seqlens.has_value(), "compressor: In TH layout, tensor cu_seqlens should not be None");
+    TORCH_CHECK(th || !cu_seqlens.has_value(), "compressor: In BSH layout, tensor cu_seqlens must be None");
+    TORCH_CHECK(!cu_seqlens.has_value() || (cu_seqlens->dim() == 1 && cu_seqlens->numel() >= 1), "compressor: cu_seqlens must be [batch + 1]");
+    TORCH_CHECK(!seqused.has_value() || seqused->dim() == 1, "compressor: seqused must be 1-dimensional");
+    TORCH_CHECK(!start_pos.has_value() || start_pos->dim() == 1, "compressor: start_pos must be 1-dimensional");
+    TORCH_CHECK(coff == 1 || coff == 2, "compressor: coff only supports 1 or 2");
+    TORCH_CHECK(cmp_ratio >= 1 && cmp_ratio <= 128, "compressor: cmp_ratio out of range");
+    const int64_t D = norm_weight.size(0), H = x.size(x.dim() - 1), ww = coff * D;
+    const int64_t B = th ? cu_seqlens->numel() - 1 : x.size(0), S = th ? 0 : x.size(1), T = th ? x.size(0) : B * S;
+    TORCH_CHECK(B <= INT32_MAX && S <= INT32_MAX, "compressor: batch size");
+    const int64_t cg = th ? 0 : (S + cmp_ratio - 1) / cmp_ratio, out_rows = th ? std::min(T, T / cmp_ratio + B) : B * cg;
+    auto dim_is = [](const at::Tensor &t, int64_t dim, int64_t want, const char *name, const char *what) {
+        TORCH_CHECK(t.size(dim) == want, "compressor: ", name, " shape dim ", dim, " should be equal to ", what, ": ", want, ", but got ", t.size(dim));
+    };
+    dim_is(wkv, 1, H, "wkv", "hiddenSize"), dim_is(wgate, 1, H, "wgate", "hiddenSize");
+    dim_is(wkv, 0, ww, "wkv", "coff*headDim"), dim_is(wgate, 0, ww, "wgate", "coff*headDim");
+    dim_is(state_cache, 2, 2 * ww, "state_cache", "2*coff*headDim");
+    dim_is(ape, 1, ww, "ape", "coff*headDim"), dim_is(ape, 0, cmp_ratio, "ape", "cmpRatio");
+    dim_is(*state_block_table, 0, B, "state_block_table", "batchSize");
+    if (seqused.has_value()) dim_is(*seqused, 0, B, "seqused", "batchSize");
+    if (start_pos.has_value()) dim_is(*start_pos, 0, B, "start_pos", "batchSize");
+    if (th) {
+        dim_is(rope_sin, 0, out_rows, "rope_sin", "min(tokenSize, tokenSize/cmpRatio+batchSize)");
+        dim_is(rope_cos, 0, out_rows, "rope_cos", "min(tokenSize, tokenSize/cmpRatio+batchSize)");
+        dim_is(rope_sin, 1, rope_head_dim, "rope_sin", "ropeHeadDim"), dim_is(rope_cos, 1, rope_head_dim, "rope_cos", "ropeHeadDim");
+    } else {
+        dim_is(rope_sin, 0, B, "rope_sin", "batchSize"), dim_is(rope_cos, 0, B, "rope_cos", "batchSize");
+        dim_is(rope_sin, 1, cg, "rope_sin", "ceil(seqSize/cmpRatio)"), dim_is(rope_cos, 1, cg, "rope_cos", "ceil(seqSize/cmpRatio)");
+        dim_is(rope_sin, 2, rope_head_dim, "rope_sin", "ropeHeadDim"), dim_is(rope_cos, 2, rope_head_dim, "rope_cos", "ropeHeadDim");
+    }
+    TORCH_CHECK(state_cache.is_contiguous(), "compressor: state_cache must be contiguous");
+
+    at::Tensor cmp_kv = th ? at::empty({out_rows, D}, x.options()) : at::empty({B, cg, D}, x.options());
+    const bool launch = T > 0 && B > 0;
+    const at::Tensor xc = x.contiguous(), wk = wkv.contiguous(), wg = wgate.contiguous(), ap = ape.contiguous(), nw = norm_weight.contiguous();
+    const at::Tensor rs = rope_sin.contiguous(), rc = rope_cos.contiguous();
+    auto contig = [](const std::optional<at::Tensor> &t) { return t.has_value() ? std::optional<at::Tensor>(t->contiguous()) : std::nullopt; };
+    const std::optional<at::Tensor> tb = contig(state_block_table), cu = contig(cu_seqlens), su = contig(seqused), sp = contig(start_pos);
+    auto iptr = [](const std::optional<at::Tensor> &t) { return t.has_value() ? t->data_ptr<int>() : nullptr; };
+    const size_t wsb = launch ? mi_compressor_workspace(T, (int)B, (int)H, (int)D, (int)coff) : 0;
+    at::Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 16)}, at::dtype(at::kByte).device(x.device()));
+    mi_compressor_params p{};
+    p.x = xc.data_ptr(), p.wkv = wk.data_ptr(), p.wgate = wg.data_ptr(), p.state_cache = state_cache.data_ptr<float>();
+    p.ape = ap.data_ptr<float>(), p.norm_weight = nw.data_ptr<float>(), p.rope_sin = rs.data_ptr<float>(), p.rope_cos = rc.data_ptr<float>();
+    p.state_block_table = iptr(tb), p.cu_seqlens = iptr(cu), p.seqused = iptr(su), p.start_pos = iptr(sp);
+    p.cmp_kv = cmp_kv.data_ptr(), p.workspace = ws.data_ptr(), p.workspace_bytes = wsb;
+    p.tokens = T, p.out_rows = out_rows, p.state_blocks = state_cache.size(0), p.table_stride = tb->dim() == 2 ? tb->stride(0) : 1;
+    p.state_cache_stride_dim0 = state_cache_stride_dim0;
+    p.layout = th ? MI_COMPRESSOR_TH : MI_COMPRESSOR_BSH, p.batch = (int)B, p.seq = (int)S, p.hidden = (int)std::min<int64_t>(H, INT32_MAX);
+    p.head_dim = (int)std::min<int64_t>(D, INT32_MAX), p.cmp_ratio = (int)cmp_ratio, p.coff = (int)coff;
+    p.rope_head_dim = (int)std::min<int64_t>(std::max<int64_t>(rope_head_dim, 0), INT32_MAX);
+    p.rotary_mode = (int)std::min<int64_t>(std::max<int64_t>(rotary_mode, -1), 64), p.cache_mode = (int)std::min<int64_t>(std::max<int64_t>(cache_mode, -1), 64);
+    p.block_size = (int)std::min<int64_t>(state_cache.size(1), INT32_MAX), p.table_dims = (int)tb->dim();
+    p.table_cols = tb->dim() == 2 ? (int)std::min<int64_t>(tb->size(1), INT32_MAX) : 1, p.dtype = dtype_code(x), p.norm_eps = (float)norm_eps;
+    const int rc_ = mi_compressor(&p, cur_stream());
+    TORCH_CHECK(rc_ == 0, "mi_compressor failed with code ", rc_,
+                " ((cmp_ratio, coff, head_dim) must be (4, 2, 512), (4, 2, 128) or (128, 1, 512); 1024 <= hidden <= 10240 and a multiple of 512; "
+                "rope_head_dim 64; rotary_mode 1 or 2; cache_mode 1 or 2, in mode 2 a 2-D table of at least coff*cmp_ratio+1 columns; "
+                "state_cache_stride_dim0 0 or size(1)*size(2))");
+    return cmp_kv;
+}
+
 // SwiGLU + per-row INT8 quantisation; same arguments / returns as swiglu_quant (activation/swiglu_quant.py:87-127).
 std::tuple<at::Tensor, at::Tensor> swiglu_quant(const at::Tensor &x, const at::Tensor &group_list, int64_t group_list_type,
                                                 bool need_quant, bool do_limit, double limit)
@@ -1472,6 +1567,13 @@ TORCH_LIBRARY_FRAGMENT(npu, m)
         "int ori_mask_mode=4, int cmp_mask_mode=3, int ori_win_left=128, int ori_win_right=0, "
         "str layout_q='BSND', str layout_kv='PA_ND', "
         "bool return_softmax_lse=False) -> (Tensor, Tensor)");
+    m.def(
+        "compressor(Tensor x, Tensor wkv, Tensor wgate, Tensor! state_cache, "
+        "Tensor ape, Tensor norm_weight, Tensor rope_sin, Tensor rope_cos, "
+        "Tensor? state_block_table=None, Tensor? cu_seqlens=None, Tensor? seqused=None, "
+        "Tensor? start_pos=None, int rope_head_dim=64, int cmp_ratio=4, int coff=1, "
+        "float norm_eps=1e-6, int rotary_mode=1, int cache_mode=1, "
+        "int state_cache_stride_dim0=0) -> Tensor");
     m.def("attn_residual_mix(Tensor prefix_sum, Tensor bank, int num_valid_blocks, Tensor combined_weight, float variance_epsilon) -> Tensor");
     m.def("mul_add(Tensor routed_input, Tensor shared_input, float scaling_factor) -> Tensor");
     m.def("zero_experts_compute_identity(Tensor(a!) expert_indices, Tensor(b!) expert_scales, int num_experts, Tensor hidden_states, "
@@ -1516,6 +1618,7 @@ TORCH_LIBRARY_IMPL(npu, CUDA, m)
     m.impl("prefill_topk_from_score", TORCH_FN(sglang::npu_kernel::prefill_topk_from_score));
     m.impl("lightning_indexer", TORCH_FN(sglang::npu_kernel::lightning_indexer));
     m.impl("sparse_attn_sharedkv", TORCH_FN(sglang::npu_kernel::sparse_attn_sharedkv));
+    m.impl("compressor", TORCH_FN(sglang::npu_kernel::compressor));
     m.impl("attn_residual_mix", TORCH_FN(sglang::npu_kernel::attn_residual_mix));
     m.impl("mul_add", TORCH_FN(sglang::npu_kernel::mul_add));
     m.impl("zero_experts_compute_identity", TORCH_FN(sglang::npu_kernel::zero_experts_compute_identity));
