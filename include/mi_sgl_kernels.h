@@ -15,6 +15,7 @@
  *   mi_lightning_indexer     <- csrc/lightning_indexer/ (torch.ops.npu.lightning_indexer)
  *   mi_sparse_attn_sharedkv  <- csrc/sparse_attn_sharedkv/ (torch.ops.npu.sparse_attn_sharedkv)
  *   mi_compressor            <- csrc/compressor/ (torch.ops.npu.compressor)
+ *   mi_sparse_attention_score <- csrc/sparse_attention_score/ (torch.ops.npu.npu_sparse_attention_score)
  *   mi_swiglu_quant          <- activation/swiglu_quant.py:8-127     (_swiglu_quant_kernel / swiglu_quant)
  *   mi_add_rmsnorm_bias      <- norm/add_rmsnorm_bias.py:8-147        (add_rmsnorm_bias_kernel / add_rmsnorm_bias)
  *                               norm/add_rmsnorm_bias.py:150-232      (add_gemma_rms_norm)
@@ -44,6 +45,7 @@ extern "C" {
 #define MI_DTYPE_BF16 0
 #define MI_DTYPE_F16 1
 #define MI_DTYPE_F32 2      /* the row statistics / scalings below only */
+#define MI_DTYPE_FP8_E4M3 3 /* OCP e4m3fn; mi_sparse_attention_score only */
 
 const char *mi_sgl_kernels_version(void);
 
@@ -356,6 +358,52 @@ typedef struct mi_compressor_params {
 } mi_compressor_params;
 size_t mi_compressor_workspace(int64_t tokens, int batch, int hidden, int head_dim, int coff);
 int mi_compressor(const mi_compressor_params *params, void *stream);
+
+/* ---- block-sparse GQA attention over per-token block lists (csrc/sparse_attention_score/: torch.ops.npu.npu_sparse_attention_score) ----
+ * The multi-token (speculative-decoding verify, short extend) and FP8 sibling of mi_gqa_sparse_decode.  q [tokens, q_heads, head_dim] (TND),
+ * k / v [num_pages, block_size, kv_heads, head_dim], out [tokens, q_heads, head_dim]: strides in elements, innermost dimension contiguous.
+ * dtype MI_DTYPE_BF16 / F16: q, k, v and out alike.  MI_DTYPE_FP8_E4M3: q, k, v are 1-byte OCP e4m3fn, out is fp16.
+ * select_idx [kv_heads, Q >= tokens, topk] int32 logical block ids through the three idx strides; select_num_idx [kv_heads, Q] int32 through
+ * the two num strides (NULL: every slot is live); block_table [batch, columns] int32 through the two bt strides; actual_seq_lengths [batch]
+ * int32 query tokens per request (lengths, not cumulative; NULL: one token per request, tokens == batch); actual_seq_lengths_kv [batch] int32.
+ * Token t belongs to the request b whose running sum of actual_seq_lengths covers it and is its token j; group = q_heads / kv_heads, kv head
+ * kh serves query heads kh * group .. + group - 1.
+ *   pos = actual_seq_lengths_kv[b] - actual_seq_lengths[b] + j                    the token's own position
+ *   live slots: the first n of select_idx[kh, t, :], n = topk, or select_num_idx[kh, t] clamped to [0, topk]; a live slot with a negative id
+ *   is skipped; slots behind n are never read as block ids and nothing derived from them is dereferenced.
+ *   block lb contributes all block_size keys if lb < pos / block_size, its first pos % block_size + 1 keys if lb == pos / block_size;
+ *   duplicates count twice; out[t, h] = softmax((q . k) * sm_scale) . v over the contributing keys, no sink; fp32 scores, softmax and
+ *   accumulation, P rounded to the engine dtype (bf16 / fp16) before P.V.
+ * Defined where the reference is not: a live block with lb > pos / block_size or lb >= columns is dropped and its table entry not read; a
+ * table entry outside [0, num_pages) drops its block; an output row is zeros when the token has no contributing key, when pos < 0, or when t
+ * lies behind the sum of actual_seq_lengths (the padding rows of a graph buffer).
+ * FP8: q_dequant_scale [batch, q_heads, q_scale_blocks] fp32 contiguous, read at [b, h, pos / block_size] (a token with pos / block_size >=
+ * q_scale_blocks gives a zeros row); k_dequant_scale, v_dequant_scale [batch, kv_heads, columns] fp32 contiguous, read at [b, kh, lb].
+ * logit = (q8 . k8) * sq * sk * sm_scale; a block's value rows are v8 * sv ROUNDED TO FP16 (the scale is folded into the staged rows).  All
+ * three are required with FP8 and must be NULL otherwise.
+ * num_chunks: pieces of the list per (token, kv head), 1 <= num_chunks <= topk; 0 = mi_sparse_attention_score_num_chunks (shapes and CU
+ * count only).  More than one chunk needs mi_sparse_attention_score_workspace() bytes, 16-byte aligned, for the fp32 partials and runs a
+ * merge launch behind the attention launch.  Nothing is read back and nothing is allocated: capturable in a graph.
+ * LIMITS (MI_SGL_EINVAL beyond them, nothing launched): q_heads % kv_heads == 0; block_size 16 / 32 / 64 / 128; head_dim a multiple of 8 up
+ * to 256; FP8: head_dim 128 and block_size 128 only; 1 <= topk <= 1024; sm_scale > 0; q strides multiples of 8 elements, cache strides
+ * multiples of 8 (FP8: 16) elements, out strides multiples of 4; q 16-byte (FP8: 8-byte), caches 16-byte, out 8-byte aligned.
+ * tokens = 0 or batch = 0: MI_SGL_OK without a launch. */
+typedef struct mi_sparse_attention_score_params {
+    const void *q, *k, *v;
+    void *out;
+    const int32_t *select_idx, *select_num_idx, *block_table, *actual_seq_lengths, *actual_seq_lengths_kv;      /* select_num_idx, actual_seq_lengths: NULL allowed */
+    const float *q_dequant_scale, *k_dequant_scale, *v_dequant_scale;                                           /* FP8 only */
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t tokens;
+    int64_t q_stride_t, q_stride_h, k_stride_blk, k_stride_row, k_stride_h, v_stride_blk, v_stride_row, v_stride_h, o_stride_t, o_stride_h;
+    int64_t idx_stride_h, idx_stride_q, idx_stride_k, num_stride_h, num_stride_q, bt_stride_b, bt_stride_n;
+    int batch, q_heads, kv_heads, head_dim, block_size, topk, columns, num_pages, q_scale_blocks, dtype, num_chunks;
+    float sm_scale;
+} mi_sparse_attention_score_params;
+size_t mi_sparse_attention_score_workspace(int64_t tokens, int q_heads, int head_dim, int num_chunks);
+int mi_sparse_attention_score_num_chunks(int64_t tokens, int kv_heads, int topk);
+int mi_sparse_attention_score(const mi_sparse_attention_score_params *params, void *stream);
 
 /* ---- SwiGLU + per-row INT8 quantisation (swiglu_quant.py:87-127) -------------------------------------------------
  * x [rows, cols] (cols = 2I; gate = x[:, :I], up = x[:, I:]); only the first `total` rows are processed, where total =

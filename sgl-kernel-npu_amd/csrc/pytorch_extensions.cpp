@@ -840,6 +840,110 @@ at::Tensor compressor(const at::Tensor &x, const at::Tensor &wkv, const at::Tens
     return cmp_kv;
 }
 
+// csrc/sparse_attention_score/ (op_host/sparse_attention_score.cpp): block-sparse GQA attention over per-token block lists, the reference's
+// native main-attention op (csrc/kernels/sparse_attention_score.hip; semantics in include/mi_sgl_kernels.h).  Shapes override the
+// attributes: Hkv, Q and topK come from select_idx, batch and columns from block_table; scale_value within 1e-9 of zero means 1 / sqrt(D).
+// inner_precise is accepted and every value runs the high-precision path (fp32 scores, softmax and accumulation).  Nothing is copied to or
+// read back from the device: only the output and the workspace are allocated, from shapes.
+at::Tensor npu_sparse_attention_score(const at::Tensor &query, const at::Tensor &key, const at::Tensor &value, const at::Tensor &select_idx,
+                                      const at::Tensor &block_table, const std::optional<at::Tensor> &select_num_idx,
+                                      const std::optional<at::Tensor> &q_dequant_scale, const std::optional<at::Tensor> &k_dequant_scale,
+                                      const std::optional<at::Tensor> &v_dequant_scale, const std::optional<at::Tensor> &actual_seq_lengths,
+                                      const std::optional<at::Tensor> &actual_seq_lengths_kv, int64_t num_key_value_heads, double scale_value,
+                                      int64_t block_size, int64_t top_k, int64_t inner_precise)
+{
+    (void)num_key_value_heads, (void)top_k, (void)inner_precise;
+    const c10::DeviceGuard device_guard(query.device());
+    const auto qt = query.scalar_type();
+    const bool fp8 = qt == at::kFloat8_e4m3fn;
+    TORCH_CHECK(qt == at::kHalf || qt == at::kBFloat16 || fp8, "npu_sparse_attention_score: query must be bf16, fp16 or float8_e4m3fn");
+    TORCH_CHECK(key.scalar_type() == qt, "npu_sparse_attention_score: key must have the query's dtype");
+    TORCH_CHECK(value.scalar_type() == qt, "npu_sparse_attention_score: value must have the query's dtype");
+    TORCH_CHECK(select_idx.scalar_type() == at::kInt, "npu_sparse_attention_score: select_idx must be int32");
+    TORCH_CHECK(block_table.scalar_type() == at::kInt, "npu_sparse_attention_score: block_table must be int32");
+    TORCH_CHECK(actual_seq_lengths_kv.has_value(), "npu_sparse_attention_score: actual_seq_lengths_kv is required");
+    auto same_device = [&](const at::Tensor &t, const char *name) {
+        TORCH_CHECK(t.device() == query.device(), "npu_sparse_attention_score: ", name, " must be on the query's device");
+    };
+    auto optional_i32 = [&](const std::optional<at::Tensor> &t, const char *name) {
+        if (!t.has_value()) return;
+        TORCH_CHECK(t->scalar_type() == at::kInt, "npu_sparse_attention_score: ", name, " must be int32");
+        same_device(*t, name);
+    };
+    same_device(key, "key"), same_device(value, "value"), same_device(select_idx, "select_idx"), same_device(block_table, "block_table");
+    optional_i32(select_num_idx, "select_num_idx"), optional_i32(actual_seq_lengths, "actual_seq_lengths");
+    optional_i32(actual_seq_lengths_kv, "actual_seq_lengths_kv");
+    TORCH_CHECK(query.dim() == 3, "npu_sparse_attention_score: query must be [T, Hq, D]");
+    TORCH_CHECK(key.dim() == 4, "npu_sparse_attention_score: key must be [pages, block_size, Hkv, D]");
+    TORCH_CHECK(value.dim() == 4, "npu_sparse_attention_score: value must be [pages, block_size, Hkv, D]");
+    TORCH_CHECK(select_idx.dim() == 3, "npu_sparse_attention_score: select_idx must be [Hkv, Q, topK]");
+    TORCH_CHECK(block_table.dim() == 2, "npu_sparse_attention_score: block_table must be [batch, columns]");
+    const int64_t T = query.size(0), Hq = query.size(1), D = query.size(2);
+    const int64_t Hkv = select_idx.size(0), Q = select_idx.size(1), topk = select_idx.size(2);
+    const int64_t batch = block_table.size(0), columns = block_table.size(1);
+    TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "npu_sparse_attention_score: query heads (", Hq, ") must be a multiple of select_idx.size(0) (", Hkv, ")");
+    TORCH_CHECK(key.sizes() == value.sizes(), "npu_sparse_attention_score: key and value shapes differ");
+    TORCH_CHECK(key.size(2) == Hkv, "npu_sparse_attention_score: key.size(2) must equal select_idx.size(0)");
+    TORCH_CHECK(key.size(3) == D, "npu_sparse_attention_score: key.size(3) must equal the query's head dim");
+    TORCH_CHECK(block_size == key.size(1) && (block_size == 16 || block_size == 32 || block_size == 64 || block_size == 128),
+                "npu_sparse_attention_score: block_size must equal key.size(1) and be 16, 32, 64 or 128");
+    TORCH_CHECK(D > 0 && D % 8 == 0 && D <= 256, "npu_sparse_attention_score: query head dim must be a multiple of 8 up to 256");
+    TORCH_CHECK(!fp8 || (D == 128 && block_size == 128), "npu_sparse_attention_score: a float8_e4m3fn query needs head dim 128 and block_size 128");
+    TORCH_CHECK(Q >= T, "npu_sparse_attention_score: select_idx.size(1) (", Q, ") must cover the query's tokens (", T, ")");
+    TORCH_CHECK(topk >= 1 && topk <= 1024, "npu_sparse_attention_score: select_idx.size(2) (topK) must be in [1, 1024]");
+    TORCH_CHECK(!select_num_idx.has_value() || (select_num_idx->dim() == 2 && select_num_idx->size(0) == Hkv && select_num_idx->size(1) == Q),
+                "npu_sparse_attention_score: select_num_idx must be [Hkv, Q]");
+    TORCH_CHECK(!actual_seq_lengths.has_value() || actual_seq_lengths->numel() == batch,
+                "npu_sparse_attention_score: actual_seq_lengths must have block_table.size(0) elements");
+    TORCH_CHECK(actual_seq_lengths.has_value() || T == batch || T == 0,
+                "npu_sparse_attention_score: without actual_seq_lengths every request has one token: T must equal block_table.size(0)");
+    TORCH_CHECK(actual_seq_lengths_kv->numel() == batch, "npu_sparse_attention_score: actual_seq_lengths_kv must have block_table.size(0) elements");
+    auto scale_arg = [&](const std::optional<at::Tensor> &t, const char *name, int64_t heads, int64_t last) {
+        TORCH_CHECK(t.has_value() == fp8, "npu_sparse_attention_score: ", name, fp8 ? " is required with a float8_e4m3fn query" : " is only taken with a float8_e4m3fn query");
+        if (!fp8) return;
+        same_device(*t, name);
+        TORCH_CHECK(t->scalar_type() == at::kFloat && t->dim() == 3 && t->size(0) == batch && t->size(1) == heads && (last < 0 ? t->size(2) >= 1 : t->size(2) == last),
+                    "npu_sparse_attention_score: ", name, " must be fp32 [batch, heads, blocks]");
+    };
+    scale_arg(q_dequant_scale, "q_dequant_scale", Hq, -1);
+    scale_arg(k_dequant_scale, "k_dequant_scale", Hkv, columns);
+    scale_arg(v_dequant_scale, "v_dequant_scale", Hkv, columns);
+    TORCH_CHECK(query.stride(2) == 1 && key.stride(3) == 1 && value.stride(3) == 1, "npu_sparse_attention_score: the innermost dimension of query, key and value must be contiguous");
+    const double scale = std::fabs(scale_value) <= 1e-9 ? 1.0 / std::sqrt((double)D) : scale_value;
+    TORCH_CHECK(scale > 0, "npu_sparse_attention_score: scale_value must be positive (or 0 for 1 / sqrt(D))");
+
+    at::Tensor out = at::empty({T, Hq, D}, query.options().dtype(fp8 ? at::kHalf : qt));
+    if (T == 0 || batch == 0) return out.zero_();
+    const int chunks = mi_sparse_attention_score_num_chunks(T, (int)Hkv, (int)topk);
+    const size_t wsb = mi_sparse_attention_score_workspace(T, (int)Hq, (int)D, chunks);
+    at::Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 16)}, at::dtype(at::kByte).device(query.device()));
+    // contiguous() copies on the device, in stream order, only where a view is passed
+    const at::Tensor qlen = actual_seq_lengths.has_value() ? actual_seq_lengths->contiguous() : at::Tensor();
+    const at::Tensor kvlen = actual_seq_lengths_kv->contiguous();
+    at::Tensor sq, sk, sv;
+    if (fp8) sq = q_dequant_scale->contiguous(), sk = k_dequant_scale->contiguous(), sv = v_dequant_scale->contiguous();
+    mi_sparse_attention_score_params p{};
+    p.q = query.data_ptr(), p.k = key.data_ptr(), p.v = value.data_ptr(), p.out = out.data_ptr();
+    p.select_idx = select_idx.data_ptr<int>(), p.select_num_idx = select_num_idx.has_value() ? select_num_idx->data_ptr<int>() : nullptr;
+    p.block_table = block_table.data_ptr<int>(), p.actual_seq_lengths = qlen.defined() ? qlen.data_ptr<int>() : nullptr;
+    p.actual_seq_lengths_kv = kvlen.data_ptr<int>();
+    if (fp8) p.q_dequant_scale = sq.data_ptr<float>(), p.k_dequant_scale = sk.data_ptr<float>(), p.v_dequant_scale = sv.data_ptr<float>();
+    p.workspace = ws.data_ptr(), p.workspace_bytes = wsb, p.tokens = T;
+    p.q_stride_t = query.stride(0), p.q_stride_h = query.stride(1), p.k_stride_blk = key.stride(0), p.k_stride_row = key.stride(1), p.k_stride_h = key.stride(2);
+    p.v_stride_blk = value.stride(0), p.v_stride_row = value.stride(1), p.v_stride_h = value.stride(2), p.o_stride_t = out.stride(0), p.o_stride_h = out.stride(1);
+    p.idx_stride_h = select_idx.stride(0), p.idx_stride_q = select_idx.stride(1), p.idx_stride_k = select_idx.stride(2);
+    if (select_num_idx.has_value()) p.num_stride_h = select_num_idx->stride(0), p.num_stride_q = select_num_idx->stride(1);
+    p.bt_stride_b = block_table.stride(0), p.bt_stride_n = block_table.stride(1);
+    p.batch = (int)batch, p.q_heads = (int)Hq, p.kv_heads = (int)Hkv, p.head_dim = (int)D, p.block_size = (int)block_size, p.topk = (int)topk;
+    p.columns = (int)std::min<int64_t>(columns, INT32_MAX), p.num_pages = (int)std::min<int64_t>(key.size(0), INT32_MAX);
+    p.q_scale_blocks = fp8 ? (int)std::min<int64_t>(sq.size(2), INT32_MAX) : 0;
+    p.dtype = fp8 ? MI_DTYPE_FP8_E4M3 : dtype_code(query), p.num_chunks = chunks, p.sm_scale = (float)scale;
+    const int rc = mi_sparse_attention_score(&p, cur_stream());
+    TORCH_CHECK(rc == 0, "mi_sparse_attention_score failed with code ", rc,
+                " (strides of query multiples of 8 elements, of key / value multiples of 8 -- float8: 16 -- elements; 16-byte aligned tensors)");
+    return out;
+}
+
 // SwiGLU + per-row INT8 quantisation; same arguments / returns as swiglu_quant (activation/swiglu_quant.py:87-127).
 std::tuple<at::Tensor, at::Tensor> swiglu_quant(const at::Tensor &x, const at::Tensor &group_list, int64_t group_list_type,
                                                 bool need_quant, bool do_limit, double limit)
@@ -1568,6 +1672,13 @@ TORCH_LIBRARY_FRAGMENT(npu, m)
         "str layout_q='BSND', str layout_kv='PA_ND', "
         "bool return_softmax_lse=False) -> (Tensor, Tensor)");
     m.def(
+        "npu_sparse_attention_score(Tensor query, Tensor key, Tensor value, Tensor select_idx, "
+        "Tensor block_table, Tensor? select_num_idx=None, Tensor? q_dequant_scale=None, "
+        "Tensor? k_dequant_scale=None, Tensor? v_dequant_scale=None, "
+        "Tensor? actual_seq_lengths=None, Tensor? actual_seq_lengths_kv=None, "
+        "int num_key_value_heads=1, float scale_value=1.0, int block_size=128, "
+        "int top_k=16, int inner_precise=0) -> Tensor");
+    m.def(
         "compressor(Tensor x, Tensor wkv, Tensor wgate, Tensor! state_cache, "
         "Tensor ape, Tensor norm_weight, Tensor rope_sin, Tensor rope_cos, "
         "Tensor? state_block_table=None, Tensor? cu_seqlens=None, Tensor? seqused=None, "
@@ -1619,6 +1730,7 @@ TORCH_LIBRARY_IMPL(npu, CUDA, m)
     m.impl("lightning_indexer", TORCH_FN(sglang::npu_kernel::lightning_indexer));
     m.impl("sparse_attn_sharedkv", TORCH_FN(sglang::npu_kernel::sparse_attn_sharedkv));
     m.impl("compressor", TORCH_FN(sglang::npu_kernel::compressor));
+    m.impl("npu_sparse_attention_score", TORCH_FN(sglang::npu_kernel::npu_sparse_attention_score));
     m.impl("attn_residual_mix", TORCH_FN(sglang::npu_kernel::attn_residual_mix));
     m.impl("mul_add", TORCH_FN(sglang::npu_kernel::mul_add));
     m.impl("zero_experts_compute_identity", TORCH_FN(sglang::npu_kernel::zero_experts_compute_identity));
